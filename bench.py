@@ -11,6 +11,16 @@ Frames shard by frame across ranks (weak scaling: --frames per GPU); no data-pat
 itself (torch.distributed.run, one process per GPU, RCCL); under the driver's own torchrun launch it
 is simply one of the ranks.
 
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last timed step when
+--dump-outputs DIR is given, and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything below: the per-kernel table and roofline, the other configs, the CPU
+baseline and the checks against the oracle and the golden checksums.
+
+--dump-outputs DIR (rank 0's share): configs[1] writes thr.npy (every frame's Otsu threshold) and
+dst_sample.npy (a fixed, seeded sample of 2^23 pixels of the thresholded edge maps); configs[4]
+writes counts.npy and rects.npy (every frame's gs_rect list, concatenated in frame order).  float32,
+at most 64 MB in all; the inputs depend on the arguments only, so two builds compare output for output.
+
 roofline: the dominant kernel of the timed step (the fused blur+sobel+histogram kernel), timed live
 with HIP events on the stream it is launched on.  `frac` is PHYSICAL: the bytes the launch moves
 (1 read + 1 write per pixel; PMC traffic beside it) / time / 8 TB/s.  The kernel is VALU-bound, so
@@ -285,6 +295,30 @@ def wsum_bytes(np, a):
     return int(np.sum(np.arange(1, b.size + 1, dtype=np.uint64) * (b + np.uint64(1)), dtype=np.uint64))
 
 
+DUMP_SAMPLE_PX = 1 << 23  # 32 MB as float32
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_pixels(np, torch, img):
+    """a fixed, seeded sample of a device image batch (the same flat indices for the same shape), ascending index order"""
+    n = img.numel()
+    if n <= DUMP_SAMPLE_PX:
+        return img.reshape(-1).cpu().numpy()
+    idx = np.sort(np.random.default_rng(20261015).integers(0, n, DUMP_SAMPLE_PX, dtype=np.int64))
+    return img.reshape(-1)[torch.from_numpy(idx).to(img.device)].cpu().numpy()
+
+
+def dump_outputs(d, np, **arrays):
+    """--dump-outputs: DIR/<name>.npy in float32 (exact for the u8 / small-integer outputs here)"""
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    nbytes = sum(a.nbytes for a in out.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        sys.exit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (nbytes, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -355,6 +389,25 @@ def run_cfg4(args, sh, g, torch, np, w, h, F, r, lo, total):
     dt_local = time.perf_counter() - t0
     sh.barrier()
     dt = sh.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and sh.rank == 0:  # every frame's rect list, concatenated in frame order (at most 2^21 records)
+        cn, rc = counts.cpu().numpy(), rects.cpu().numpy()
+        recs = np.concatenate([rc[f, :cn[f]] for f in range(F)] + [np.zeros((0, 4), np.int32)])[:1 << 21]
+        dump_outputs(args.dump_outputs, np, counts=cn, rects=recs)
+    head = {
+        "metric": "frames/s for gs_blur->gs_sobel->gs_integral->gs_lbp_detect on 4K uint8 (BASELINE configs[4])",
+        "value": round(total * args.steps / dt, 2), "unit": "frames/s", "n_gpus": sh.world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": "configs[4]: %d frames %dx%d on this GPU, %d in total, sharded by frame" % (F, w, h, total),
+                   "frames_per_gpu": F, "global_frames": total},
+        "backend": sh.backend,
+    }
+    if not args.full:
+        if sh.rank == 0:
+            print(json.dumps(head))
+        dc.close()
+        sh.close()
+        return
     rank_ms = rank_times(sh, torch, dt_local, args.steps)
     g.lbp_count_evaluated(evaluated)  # one more, untimed step with the counting build of the cascade kernel
     step()
@@ -397,22 +450,16 @@ def run_cfg4(args, sh, g, torch, np, w, h, F, r, lo, total):
                       % (len(checked), total, frame_ranges(checked), "; frame 0 bit-exact vs %s oracle live" % o.kind if live else ""))
     ranks_seen = sh.ranks_seen()  # a collective: every rank takes part (it used to sit inside rank 0's print -- found by the 8-rank rehearsal)
     if sh.rank == 0:
-        print(json.dumps({
-            "metric": "frames/s for gs_blur->gs_sobel->gs_integral->gs_lbp_detect on 4K uint8 (BASELINE configs[4])",
-            "value": round(total * args.steps / dt, 2), "unit": "frames/s", "n_gpus": sh.world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "configs[4]: %d frames %dx%d on this GPU, %d in total, sharded by frame" % (F, w, h, total),
-                       "frames_per_gpu": F, "global_frames": total},
+        print(json.dumps(dict(head, **{
             "Mpix/s": round(total * w * h * args.steps / dt / 1e6, 1),
             "windows_per_frame_full_scan": nwin,
             "windows_evaluated_per_frame": round(ev_total / (total * args.steps), 1),
             "Gwindows/s_evaluated": round(ev_total / dt / 1e9, 2),
-            "rccl_ranks_seen": ranks_seen, "backend": sh.backend, "rank_ms_per_step": rank_ms,
+            "rccl_ranks_seen": ranks_seen, "rank_ms_per_step": rank_ms,
             "collectives": ["broadcast(cascade blob, %d B)" % len(blob), "barrier", "all_reduce(max, sum)",
                             "all_gather(counts)", "all_gather(packed gs_rect lists, %d records)" % int(all_rects.shape[0])],
             "parity": parity,
-            "detections_total": int(all_counts.sum()), "detections_first_frames": all_counts[:4].cpu().tolist()}))
+            "detections_total": int(all_counts.sum()), "detections_first_frames": all_counts[:4].cpu().tolist()})))
     dc.close()
     sh.close()
 
@@ -457,7 +504,14 @@ def main():
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--verify-live", action="store_true", help="cfg4: also run frame 0 through the CPU oracle (~30 s)")
     ap.add_argument("--no-other", action="store_true", help="skip the other_configs / per-kernel extras (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel table and roofline, other configs, CPU baseline, checks against the "
+                         "oracle / golden checksums (--no-cpu, --no-other, --no-verify, --verify-live trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB, rank 0's share)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     spawn_ranks_if_needed(args)
 
     import numpy as np
@@ -509,13 +563,15 @@ def main():
     def step_unfused():  # the same chain as separate per-call kernels (blurred frames materialised)
         g.edge_pipeline_batch(dst, tmp, src, r, hist, thr)
 
-    # the library brackets every launch of the dominant (fused) kernel with HIP events on the stream
+    # --full: the library brackets every launch of the dominant (fused) kernel with HIP events on the stream
     # it is launched on -- during the timed steps themselves; the pairs are created beforehand
     launches_per_step = (F + 31) // 32
-    g.profile(max(2, (args.steps + args.warmup) * launches_per_step + 8))
+    if args.full:
+        g.profile(max(2, (args.steps + args.warmup) * launches_per_step + 8))
     for _ in range(args.warmup):
         step()
-    g.profile_read()  # drop the warm-up launches
+    if args.full:
+        g.profile_read()  # drop the warm-up launches
     sh.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -525,12 +581,31 @@ def main():
     dt_local = time.perf_counter() - t0
     sh.barrier()
     dt = sh.max_over_ranks(time.perf_counter() - t0)
+    value = float(total) * w * h * args.steps / dt / 1e6
+    ms_step = dt / args.steps * 1e3
+    if args.dump_outputs and sh.rank == 0:  # before anything else writes dst
+        dump_outputs(args.dump_outputs, np, thr=thr.cpu().numpy(), dst_sample=sample_pixels(np, torch, dst))
+    head = {
+        "metric": BASELINE_METRIC,  # BASELINE.json's metric string; the workload is named in config.workload
+        "value": round(value, 1), "unit": "Mpix/s", "n_gpus": sh.world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": "configs[1]: gs_blur(r=%d) -> gs_sobel -> gs_otsu_threshold -> gs_threshold, "
+                               "%dx%d uint8, %d frames on this GPU resident in HBM (%d in the job, %s scaling)" % (r, w, h, F, total, args.scaling),
+                   "frames_per_gpu": F, "global_frames": total, "sharding": "by frame, contiguous balanced blocks, no data-path collective",
+                   "chain_algorithmic_bytes_per_px_unfused": 7, "hbm_peak_GBs": HBM_PEAK_GBS},
+        "backend": sh.backend,
+    }
+    if not args.full:
+        if sh.rank == 0:
+            print(json.dumps(head))
+        sh.close()
+        return
     rank_ms = rank_times(sh, torch, dt_local, args.steps)
     nl, tot_ms = g.profile_read()  # launches of the timed region
     g.profile(False)
     npx = F * w * h
-    value = float(total) * w * h * args.steps / dt / 1e6
-    ms_step = dt / args.steps * 1e3
 
     # ---- per-kernel timing on the launch stream (after the timed region) -------------------
     reps = max(5, min(args.steps, 20))
@@ -684,17 +759,9 @@ def main():
         digest = ((digest ^ v) * 1099511628211) & 0xffffffffffffffff
     ranks_seen = sh.ranks_seen()
 
-    out = {
-        "metric": BASELINE_METRIC,  # BASELINE.json's metric string; the workload is named in config.workload
-        "value": round(value, 1), "unit": "Mpix/s", "n_gpus": sh.world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": "configs[1]: gs_blur(r=%d) -> gs_sobel -> gs_otsu_threshold -> gs_threshold, "
-                               "%dx%d uint8, %d frames on this GPU resident in HBM (%d in the job, %s scaling)" % (r, w, h, F, total, args.scaling),
-                   "frames_per_gpu": F, "global_frames": total, "sharding": "by frame, contiguous balanced blocks, no data-path collective",
-                   "chain_algorithmic_bytes_per_px_unfused": 7, "hbm_peak_GBs": HBM_PEAK_GBS},
-        "rccl_ranks_seen": ranks_seen, "backend": sh.backend, "rank_ms_per_step": rank_ms,
+    out = dict(head)
+    out.update({
+        "rccl_ranks_seen": ranks_seen, "rank_ms_per_step": rank_ms,
         "fused": {"ms_per_step": round(ms_fused, 4), "Mpix/s": round(npx / ms_fused / 1e3, 1),
                   "hbm_bytes_per_px": 4, "hbm_GB/s": round(4.0 * npx / ms_fused / 1e6, 1),
                   "hbm_frac_of_peak": round(4.0 * npx / ms_fused / 1e6 / HBM_PEAK_GBS, 4), "note": "blur+sobel+histogram in one kernel per 32-frame chunk; each chunk's threshold pass runs under the next chunk's fused kernel"},
@@ -710,7 +777,7 @@ def main():
         "otsu_thresholds_gathered": int(thr_all.numel()),
         "parity_golden": golden_note, "parity_oracle_kind": oracle_kind,
         "output_checksum_of_checksums": "%016x" % digest, "output_checksums_gathered": int(sums_all.numel()),
-    }
+    })
     if sh.rank == 0 and sh.world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(w, h, r)
     if sh.rank == 0:

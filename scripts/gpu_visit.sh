@@ -4,9 +4,9 @@
 # Sections (rounds 2-4 had one script per visit, ~50 of them; this is their union):
 #   smoke        __graft_entry__.smoke()
 #   suite        pytest -m gpu (everything);  suite:EXPR  pytest -m gpu -k EXPR
-#   bench        python bench.py (the driver's default line)
-#   cfg4         bench.py --workload cfg4 --frames 128 (configs[4], golden-checked)
-#   strong       bench.py --scaling strong --frames 4096 (the whole batch on this GPU: the denominator of north_star's ratio)
+#   bench        python bench.py --full (the headline plus roofline, per-kernel table, other configs, checks, CPU baseline)
+#   cfg4         bench.py --full --workload cfg4 --frames 128 (configs[4], golden-checked)
+#   strong       bench.py --full --scaling strong --frames 4096 (the whole batch on this GPU: the denominator of north_star's ratio)
 #   rccl1        bench.py under torch.distributed.run, one rank, GS_BENCH_FORCE_DIST=1 (nccl == RCCL at world 1)
 #   rehearsal    bench.py --gpus 8 over gloo on this one GPU: weak, strong, cfg4 with ranks that own no frame
 #   prof         rocprofv3 --kernel-trace --stats of the bench command
@@ -23,26 +23,27 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R; mkdir -p gpurun_out; export TMPDIR=/tmp
 TAG=${1:?usage: gpu_visit.sh TAG section...}; shift
 O=gpurun_out/$TAG
+D=$(dirname $O)  # where the logs and traces go
 for sec in "$@"; do
   arg=${sec#*:}; [ "$arg" = "$sec" ] && arg=""
   echo "== $sec"
   case ${sec%%:*} in
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee ${O}_smoke.log ;;
     suite) timeout 2400 python -m pytest tests -m gpu -q ${arg:+-k "$arg"} --timeout 900 -p no:cacheprovider --durations=5 2>&1 | tail -12 | tee ${O}_pytest_gpu.log ;;
-    bench) timeout 900 python bench.py 2>${O}_bench.err | tee ${O}_bench.json | cut -c1-600; tail -3 ${O}_bench.err ;;
-    cfg4) timeout 900 python bench.py --workload cfg4 --frames 128 --steps 1 --warmup 1 2>${O}_cfg4.err | tee ${O}_bench_cfg4.json | cut -c1-1200 ;;
-    strong) timeout 900 python bench.py --scaling strong --frames 4096 --steps 10 --warmup 2 --no-cpu --no-other 2>${O}_strong.err | tee ${O}_bench_strong4096_n1.json | cut -c1-500 ;;
-    rccl1) GS_BENCH_FORCE_DIST=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29631 bench.py --gpus 1 --no-other --no-cpu --steps 20 2>${O}_rccl1.err | grep '^{' | tee ${O}_bench_rccl_world1.json | cut -c1-400 ;;
+    bench) timeout 900 python bench.py --full 2>${O}_bench.err | tee ${O}_bench.json | cut -c1-600; tail -3 ${O}_bench.err ;;
+    cfg4) timeout 900 python bench.py --full --workload cfg4 --frames 128 --steps 1 --warmup 1 2>${O}_cfg4.err | tee ${O}_bench_cfg4.json | cut -c1-1200 ;;
+    strong) timeout 900 python bench.py --full --scaling strong --frames 4096 --steps 10 --warmup 2 --no-cpu --no-other 2>${O}_strong.err | tee ${O}_bench_strong4096_n1.json | cut -c1-500 ;;
+    rccl1) GS_BENCH_FORCE_DIST=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29631 bench.py --gpus 1 --full --no-other --no-cpu --steps 20 2>${O}_rccl1.err | grep '^{' | tee ${O}_bench_rccl_world1.json | cut -c1-400 ;;
     rehearsal)
       for mode in weak strong; do
-        GS_BENCH_BACKEND=gloo GS_BENCH_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling $mode --frames $([ $mode = weak ] && echo 8 || echo 64) --steps 3 --warmup 1 --no-cpu --no-other 2>${O}_reh_$mode.err | grep '^{' | tee ${O}_bench_8rank_rehearsal_gloo_$mode.json | cut -c1-700
+        GS_BENCH_BACKEND=gloo GS_BENCH_DEVICE=0 timeout 900 python bench.py --gpus 8 --full --scaling $mode --frames $([ $mode = weak ] && echo 8 || echo 64) --steps 3 --warmup 1 --no-cpu --no-other 2>${O}_reh_$mode.err | grep '^{' | tee ${O}_bench_8rank_rehearsal_gloo_$mode.json | cut -c1-700
         tail -2 ${O}_reh_$mode.err
       done
-      GS_BENCH_BACKEND=gloo GS_BENCH_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling strong --workload cfg4 --frames 5 --steps 1 --warmup 1 2>${O}_reh_cfg4.err | grep '^{' | tee ${O}_bench_8rank_rehearsal_gloo_cfg4.json | cut -c1-1500
+      GS_BENCH_BACKEND=gloo GS_BENCH_DEVICE=0 timeout 900 python bench.py --gpus 8 --full --scaling strong --workload cfg4 --frames 5 --steps 1 --warmup 1 2>${O}_reh_cfg4.err | grep '^{' | tee ${O}_bench_8rank_rehearsal_gloo_cfg4.json | cut -c1-1500
       tail -2 ${O}_reh_cfg4.err ;;
     prof)
       rm -rf gpurun_out/prof
-      (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof -o stats -- python $R/bench.py --no-cpu --no-verify > $R/${O}_prof_bench.json 2> $R/${O}_prof.err)
+      (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$D/prof -o stats -- python $R/bench.py --full --no-cpu --no-verify > $R/${O}_prof_bench.json 2> $R/${O}_prof.err)
       f=$(find gpurun_out/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" ${O}_bench_kernel_stats.csv && head -30 "$f" | cut -c1-150 ;;
     pmc)
       rm -rf gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE

@@ -115,3 +115,21 @@ def test_stamped_measurement_files_describe_the_kernels_in_the_tree():
     b = _bench()
     d, stamp = b.measurement(os.path.join(ROOT, "profiles", "fused_isa_mix.json"))
     assert d is not None and stamp["kernel_sources_unchanged"] is True
+
+
+def test_dump_outputs_are_a_fixed_sample_in_float32(tmp_path):
+    """--dump-outputs: the same pixels of the same shape on every run, float32 files, the 64 MB limit enforced"""
+    import numpy as np
+    import torch
+    b = _bench()
+    img = torch.arange(3 * 2048 * 2048, dtype=torch.int64).remainder(251).to(torch.uint8).reshape(3, 2048, 2048)
+    s1, s2 = b.sample_pixels(np, torch, img), b.sample_pixels(np, torch, img.clone())
+    assert s1.shape == (b.DUMP_SAMPLE_PX,) and np.array_equal(s1, s2) and len(np.unique(s1)) == 251
+    small = img[:1, :64, :64]
+    assert np.array_equal(b.sample_pixels(np, torch, small), small.reshape(-1).numpy())
+    b.dump_outputs(str(tmp_path / "d"), np, thr=np.arange(5, dtype=np.uint8), dst_sample=s1)
+    thr, dst = np.load(tmp_path / "d" / "thr.npy"), np.load(tmp_path / "d" / "dst_sample.npy")
+    assert thr.dtype == dst.dtype == np.float32 and thr.tolist() == [0, 1, 2, 3, 4] and np.array_equal(dst, s1)
+    with pytest.raises(SystemExit):
+        b.dump_outputs(str(tmp_path / "e"), np, big=np.zeros(b.DUMP_LIMIT_BYTES // 4 + 1, np.float32))
+    assert not (tmp_path / "e").exists()
