@@ -80,12 +80,21 @@ unsigned gsh_profile_read(double *total_ms) {
   return n;
 }
 void gsh_tune(int key, int value) {
+  /* retired keys and values forced paths that have been removed (include/grayskull_hip.h); the keys that change results exist in
+   * experiment builds only */
+  const bool retired = key == 2 || key == 3 || key == 10 || key == 17 || key == 21 || key == 24 ||
+                       (key == 6 && (value == 1 || value == 2 || value == 5 || value == 6)) || (key == 13 && value >= 3) ||
+                       (key == 14 && (value == -1 || value >= 5));
 #ifndef GS_EXPERIMENT
-  if ((key == 16 || key == 22 || key == 23) && value != 0) { /* the keys that change results exist in experiment builds only */
-    fprintf(stderr, "grayskull_hip: gsh_tune(%d, %d) ignored: that probe needs a -DGS_EXPERIMENT build (make experiment)\n", key, value);
+  const bool probe = key == 16 || key == 22 || key == 23;
+#else
+  const bool probe = false;
+#endif
+  if ((retired || probe) && value != 0) {
+    fprintf(stderr, "grayskull_hip: gsh_tune(%d, %d) ignored: %s\n", key, value,
+            retired ? "retired, the path it forced was removed" : "that probe needs a -DGS_EXPERIMENT build (make experiment)");
     return;
   }
-#endif
   if (key >= 0 && key < 32) g_tune.set(key, value);
 }
 void gsh_sync(void) { ctx().sync(); }

@@ -277,14 +277,14 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
   /* XCD-aware chunk mapping (k_lbp.h) once the integral image no longer fits one XCD's 4 MB L2: 1080p -3 %, 4K block
    * noise -4 %, 4K edge maps -12 % (5.76 -> 5.08 ms per frame); 720p (3.7 MB) is 1-4 % better off in dispatch order
    * (profiles/r02l_lbp_xcd.log).  Key 13: 1 = never, 2 = always. */
-  a.xcd_swizzle = g_tune[13] == 1 ? 0u : g_tune[13] >= 2 ? 1u : ((a.frame_stride * 4 >= (size_t)6 << 20 && topo().eight_xcds()) ? 1u : 0u);
+  a.xcd_swizzle = g_tune[13] == 1 ? 0u : g_tune[13] == 2 ? 1u : ((a.frame_stride * 4 >= (size_t)6 << 20 && topo().eight_xcds()) ? 1u : 0u);
   /* k_lbp_tile's tiles go out in dispatch order = the reference's scan order within a scale, whatever the table's size: a
    * tile is read once into the LDS, so the L2 mapping is worth 1 % (eighths: 1080p block noise 0.621 vs 0.628 ms), while a
    * frame that reaches max_rects stops evaluating sooner when the tiles before the cap run first -- configs[4]'s 4K edge maps
    * (4096 rectangles reached in the last scale) 3.41 -> 3.19 ms per frame; per scale, uncapped, the two mappings are equal
-   * (profiles/r05j_lbp_xcd*.log).  Key 13 = 2: eighths for the tiles too; 16 + G: runs of G tiles dealt round the XCDs
-   * (not kept: 2 and 4 equal dispatch order, 8 and 16 are 1-10 % slower). */
-  const unsigned tile_map = g_tune[13] >= 17 ? (unsigned)g_tune[13] : g_tune[13] == 2 ? 1u : 0u;
+   * (profiles/r05j_lbp_xcd*.log; runs of 2 / 4 tiles dealt round the XCDs equal dispatch order, 8 and 16 are 1-10 % slower).
+   * Key 13 = 2: eighths for the tiles too. */
+  const unsigned tile_map = g_tune[13] == 2 ? 1u : 0u;
   const size_t lds = (size_t)dc->nstages * sizeof(LbpStage) +
                      (size_t)dc->nweaks * (sizeof(LbpWeak) + sizeof(LbpGeom)) + (size_t)dc->nsub * 4;
   GS_ASSERT(lds <= 60 * 1024 && "cascade tables must fit the block's LDS");
@@ -319,7 +319,6 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
     /* preset 0 (default): first re-packing point chosen per block between stages 2 and 8 (k_lbp.h) */
     ph.adaptive_max = (g_tune[4] == 0 && dc->nstages > 2) ? 8u : 0u; /* 6 .. 15 within 1.5 % (profiles/r02l_lbp_adaptive_xcd.log) */
     ph.adaptive_tenths = 2u;
-    ph.quad = g_tune[17] == 1 ? 0u : 1u; /* key 17 = 1: one lane per re-packed window (the round-2 form) */
     /* with quad-lane survivors (profiles/r03f_lbp_adaptive_quad.log, r03k_lbp_adaptive_next.log): +1 +2 +4 is best on
      * block noise (8 x 1080p 0.76 vs 0.80 ms for +1 +3 +6, 4K 3.15 vs 3.17) and within 0.5 % of the best on edge maps */
     ph.adaptive_next[0] = 1u, ph.adaptive_next[1] = 2u, ph.adaptive_next[2] = 4u;
@@ -355,8 +354,6 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
       {512, 128, 32, 3, k_lbp_tile<512, 128, 32>, k_lbp_tile<512, 128, 32, true>},
       {1024, 128, 32, 2, k_lbp_tile<1024, 128, 32>, k_lbp_tile<1024, 128, 32, true>},
       {1024, 64, 32, 2, k_lbp_tile<1024, 64, 32>, k_lbp_tile<1024, 64, 32, true>},
-      {1024, 64, 16, 2, k_lbp_tile<1024, 64, 16>, k_lbp_tile<1024, 64, 16, true>},
-      {512, 64, 32, 2, k_lbp_tile<512, 64, 32>, k_lbp_tile<512, 64, 32, true>},
   };
   constexpr int kNumCfgs = (int)(sizeof(cfgs) / sizeof(cfgs[0]));
   constexpr size_t kLdsPerCu = 160 * 1024, kLdsDyn = kLdsPerCu - 1024; /* the kernels' static __shared__ words count against the CU's LDS */
@@ -390,13 +387,13 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
     }
     /* profiles/r05c_lbp_tile_v3_own_tables_addc.log, per scale: 512 threads on 128 x 32 windows while three blocks fit a CU
      * (scales 1, 1.1), 1024 threads on it while two fit (to 2.36), then 1024 threads on 64 x 32 while two fit (to 3.45), and
-     * for what is left (3.8: 124 KB of tile) one 1024-thread block per CU still beats k_lbp_cascade (0.47 vs 0.52 ms); the
-     * last two shapes lost at every scale */
-    for (int i = 0; i < 3; i++) {
+     * for what is left (3.8: 124 KB of tile) one 1024-thread block per CU still beats k_lbp_cascade (0.47 vs 0.52 ms); two
+     * more shapes measured there (1024 threads on 64 x 16, 512 on 64 x 32) lost at every scale */
+    for (int i = 0; i < kNumCfgs; i++) {
       const unsigned b = tile_blocks(cfgs[i], sc);
       if (b >= cfgs[i].want_blocks) return Choice{i, b};
     }
-    if (g_tune[14] != -1 && tile_blocks(cfgs[1], sc) >= 1u) return Choice{1, 1u}; /* key 14 = -1: k_lbp_cascade for these */
+    if (tile_blocks(cfgs[1], sc) >= 1u) return Choice{1, 1u};
     return Choice{-1, 0};
   };
   /* Consecutive scales with the same shape AND the same blocks per CU share a launch (its dynamic LDS is the largest
@@ -425,7 +422,7 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
       for (unsigned s = s0; s < s1; s++) {
         const LbpScale &sc = gc.scales[s];
         const unsigned tx = (sc.nx + c.tw - 1) / c.tw, ty = (sc.ny + c.th - 1) / c.th;
-        const unsigned per = tile_map >= 16u ? 8u * (tile_map - 16u) : tile_map == 1u ? 8u : 1u;
+        const unsigned per = tile_map ? 8u : 1u;
         mt = std::max(mt, (tx * ty + per - 1u) / per * per);
         need = std::max(need, tile_lds(c, sc));
       }

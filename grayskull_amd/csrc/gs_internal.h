@@ -320,7 +320,6 @@ struct TuneTable {
   std::atomic<int> v[32];
   TuneTable() {
     for (auto &e : v) e.store(0, std::memory_order_relaxed);
-    v[1].store(3, std::memory_order_relaxed), v[2].store(1, std::memory_order_relaxed);
   }
   int operator[](int k) const { return v[k].load(std::memory_order_relaxed); }
   void set(int k, int x) { v[k].store(x, std::memory_order_relaxed); }
@@ -342,26 +341,24 @@ StripCfg strip_cfg(unsigned w, unsigned rows, unsigned n, unsigned waves_per_sim
 /* The strip kernels take any width >= 32 and any byte alignment of the frames (round 4): rows of a frame whose width
  * is not a multiple of 16 start at every 16-byte phase anyway (the API has no stride, ref grayskull.h:14-17), the
  * hardware serves 16-byte accesses at any address, and the ragged last strip of a row is anchored at w - 16 (k_strip.h,
- * RAGGED).  Key 21 = 1 restores the round-3 rule (multiples of 16, 16-byte aligned frames; everything else per pixel). */
-inline bool strip_ok(unsigned w, unsigned h, const void *a, const void *b) {
-  if (g_tune[21] == 1) return w % 16 == 0 && (unsigned long long)w * h < 0x7fffffffull && al16(a) && al16(b);
+ * RAGGED). */
+inline bool strip_ok(unsigned w, unsigned h) {
   return w >= 32 && (unsigned long long)w * h < 0x7fff0000ull; /* a row offset + base phase + column must not wrap 2^32 */
 }
 inline bool ragged(unsigned w) { return (w & 15u) != 0u; }
 /* which Strip flavour (k_strip.h): 0 = whole 16-px strips, rows at dword-aligned addresses; 1 = ragged width, rows still at
  * dword-aligned addresses (w % 4 == 0 and the frame at such an address): direct 16-byte loads at any 16-byte phase cost
  * nothing; 2 = any other byte phase: dword-aligned loads, realigned in registers (a 16-byte load at an address that is not
- * a multiple of 4 costs the stencils 30-45 %, profiles/r04b_byte_phase_cost.log).  Key 24 = 1: never 2 (A/B). */
+ * a multiple of 4 costs the stencils 30-45 %, profiles/r04b_byte_phase_cost.log). */
 inline int strip_mode(unsigned w, const void *src) {
   const int direct = ragged(w) ? 1 : 0;
   if ((w & 3u) == 0u && ((uintptr_t)src & 3u) == 0u) return direct;
-  if (g_tune[24] == 1) return direct;
   /* the realigning flavour places up to two more lanes per row (k_strip.h); where that opens another wave of 64 -- widths
    * just below a multiple of 1024 -- the wave costs more than the misaligned loads do (4094 x 4096: 0.39 against 0.64 of
    * the HBM peak, profiles/r04g_ragged_realign.log) */
   const unsigned strips = (w + 15) / 16;
   const unsigned lanes2 = strips + strip_realign_shift(w) + strip_realign_helper(w), lanes1 = strips + (direct ? strip_ragged_shift(w) : 0u);
-  if (g_tune[24] != 2 && (lanes2 + 63) / 64 > (lanes1 + 63) / 64) return direct;
+  if ((lanes2 + 63) / 64 > (lanes1 + 63) / 64) return direct;
   return 2;
 }
 /* kernels that still need whole 16-px strips at 16-byte aligned addresses */

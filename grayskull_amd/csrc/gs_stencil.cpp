@@ -70,10 +70,10 @@ StripCfg strip_cfg(unsigned w, unsigned rows, unsigned n, unsigned waves_per_sim
   /* block shape: 256 threads = 4 waves; a wave is 1024 px of a row.  Frames narrower than 4096 px put the spare
    * waves on further BANDS (64 x 4 up to 1024 px, 128 x 2 up to 2048 px) instead of columns that do not exist --
    * a 1920-px row kept two of a 256 x 1 block's four waves busy computing on zero fill (8 x 1080p gs_sobel at 0.21
-   * of the HBM peak).  Key 1: 0 / 1 / 2 force 64 x 4 / 256 x 1 / 128 x 2, anything else = by width. */
+   * of the HBM peak).  Key 1: 1 / 2 / 3 force 64 x 4 / 128 x 2 / 256 x 1, 0 = by width. */
   unsigned bx = 256, by = 1;
-  if (g_tune[1] == 0 || (g_tune[1] > 2 && strips <= 64)) bx = 64, by = 4;
-  else if (g_tune[1] == 2 || (g_tune[1] > 2 && strips <= 128)) bx = 128, by = 2;
+  if (g_tune[1] == 1 || (g_tune[1] == 0 && strips <= 64)) bx = 64, by = 4;
+  else if (g_tune[1] == 2 || (g_tune[1] == 0 && strips <= 128)) bx = 128, by = 2;
   c.block = dim3(bx, by);
   c.grid = dim3((strips + bx - 1) / bx, (nb + by - 1) / by, n);
   /* XCD-aware band mapping for the short-band (HBM-bound) kernels: one block per band row (w <= 4096), the band
@@ -102,7 +102,7 @@ void launch_sobel(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsi
     const unsigned nn = std::min(kMaxZ, n - f0);
     uint8_t *d = dst + fb * f0;
     const uint8_t *s = src + fb * f0;
-    if (strip_ok(w, h, d, s) && w >= 32) {
+    if (strip_ok(w, h)) {
       const int rg = strip_mode(w, s);
       const StripCfg c = strip_cfg(w, h - 2, nn, 5, 2, 6, rg);
       if (rg == 1) {
@@ -128,7 +128,7 @@ void launch_morph(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsi
     const unsigned nn = std::min(kMaxZ, n - f0);
     uint8_t *d = dst + fb * f0;
     const uint8_t *s = src + fb * f0;
-    if (strip_ok(w, h, d, s)) {
+    if (strip_ok(w, h)) {
       const int rg = strip_mode(w, s);
       const StripCfg c = strip_cfg(w, h, nn, 5, 2, 4, rg);
       if (rg == 1) GS_LAUNCH((k_morph16<DILATE, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
@@ -147,9 +147,8 @@ bool launch_integral(const uint8_t *src, unsigned w, unsigned h, unsigned n, uns
   hipStream_t st = ctx().s();
   const size_t fp = (size_t)w * h;
   /* the banded form takes any width >= 32 at any alignment (round 4: ragged rows, frames wider than 4096 px in column
-   * chunks); key 6 = 1 or key 21 = 1: the rows + columns form */
-  const bool banded = g_tune[6] != 1 && fp * 4 < 0x7fffffffull &&
-                      (g_tune[21] == 1 ? (w % 16 == 0 && w <= 4096 && al16(src) && al16(ii)) : w >= 32);
+   * chunks) */
+  const bool banded = fp * 4 < 0x7fffffffull && w >= 32;
   if (sq && !banded) return false;
   for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
     const unsigned nn = std::min(kMaxZ, n - f0);
@@ -191,9 +190,7 @@ bool launch_integral(const uint8_t *src, unsigned w, unsigned h, unsigned n, uns
         else if (wide) GS_LAUNCH((k_integral_wave<16, false, true, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
         else if (rg) GS_LAUNCH((k_integral_wave<16, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
         else GS_LAUNCH((k_integral_wave<16, false, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      } else if (g_tune[6] == 2 && !rg && !wide && w % 16 == 0) /* the block-per-band form (one barrier per row), kept for comparison */
-        GS_LAUNCH(k_integral_band, dim3(1, nb, nn), dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (nt && wide && rg) GS_LAUNCH((k_integral_wave<16, true, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
+      } else if (nt && wide && rg) GS_LAUNCH((k_integral_wave<16, true, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
       else if (nt && wide) GS_LAUNCH((k_integral_wave<16, false, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
       else if (nt && rg) GS_LAUNCH((k_integral_wave<16, true, false, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
       else if (nt) GS_LAUNCH((k_integral_wave<16, false, false, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
@@ -224,7 +221,7 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
   hipStream_t st = ctx().s();
   const size_t fp = (size_t)w * h;
   const unsigned r = std::min(radius, std::max(w, h)); /* larger windows clip identically */
-  if (g_tune[6] != 3 && r >= 1 && r <= 127 && w <= 4096 && strip_ok(w, h, dst, src)) {
+  if (g_tune[6] != 3 && r >= 1 && r <= 127 && w <= 4096 && strip_ok(w, h)) {
     /* sliding box sums straight from the source rows (k_box.h): 3-4 B/px instead of the ~16 of the integral-image
      * route below (64 4K frames: 2.8 ms whatever the radius; this one: r = 16 0.36 ms, r = 40 0.63 ms); the kernel's
      * u16 column sums and LDS halo hold up to r = 127 */
@@ -236,9 +233,8 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
        * last 16 + w % 16 columns in a launch of its own (round 5).  Round 4's RAGGED form of the ring kernels (per-pixel
        * choice between two edge divisors, shifted tail loads inside the block) was no faster than the any-radius kernel --
        * 116-152 registers at r = 4..5 instead of 84-92, one wave per SIMD from r = 12
-       * (profiles/r04k_box_ring_ragged_not_kept.log: 3838 x 2160 r = 5 0.446 vs 0.434 ms, r = 16 0.73 vs 0.53).
-       * Key 6 = 5: ragged rows on the any-radius kernel (rounds 2-4). */
-      const bool ring = g_tune[6] != 4 && !(g_tune[6] == 5 && ragged(w)) && r <= box_ring_max() && w >= 32 && h >= 2 * r + 1 &&
+       * (profiles/r04k_box_ring_ragged_not_kept.log: 3838 x 2160 r = 5 0.446 vs 0.434 ms, r = 16 0.73 vs 0.53). */
+      const bool ring = g_tune[6] != 4 && r <= box_ring_max() && w >= 32 && h >= 2 * r + 1 &&
                         (MODE == 0 || (c > -(1 << 30) && c < (1 << 30)));
       /* band height: the launch should be whole rounds of the blocks the chip holds (256 CUs x 4 of them, fewer for the
        * register-heavy ring kernels of r >= 8 / 10), and a band first loads 2r+1 rows it does not output -- loads and
@@ -281,10 +277,10 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
          * stream, ordered behind everything the caller's stream holds so far, and the caller's stream waits for it after the
          * body: it hides under the body launch instead of following it (64 x 3838x2160: r = 16 0.307 -> 0.296 ms, adaptive
          * r = 15 0.308 -> 0.292; r = 5 and 9 are 2 % better off in sequence -- profiles/r05l_box_ragged_buffer_ops.log).
-         * Key 6 = 6: always on the caller's stream, 7: always on the side stream. */
+         * Key 6 = 7: always on the side stream. */
         bool side = false;
 #ifndef GS_EMU
-        side = g_tune[6] == 7 || (g_tune[6] != 6 && r >= 12u && (size_t)nn * fp >= ((size_t)16 << 20));
+        side = g_tune[6] == 7 || (r >= 12u && (size_t)nn * fp >= ((size_t)16 << 20));
         if (side) {
           Ctx &cx = ctx();
           cx.ensure_side();
@@ -320,7 +316,7 @@ void launch_blur(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsig
   if (n == 0) return;
   hipStream_t st = ctx().s();
   const size_t fb = (size_t)w * h;
-  if (radius >= 1 && radius <= 3 && strip_ok(w, h, dst, src) && h > 2 * radius && w > 2 * radius) {
+  if (radius >= 1 && radius <= 3 && strip_ok(w, h) && h > 2 * radius && w > 2 * radius) {
     for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
       const unsigned nn = std::min(kMaxZ, n - f0);
       uint8_t *d = dst + fb * f0;
@@ -357,25 +353,19 @@ void launch_blur(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsig
  * 5.8 at 63; profiles/r02i_hist.log, r02i_hist_trips.log); a handful of frames is spread over the CUs
  * (256 CUs x 5 resident blocks) down to 16 trips per block, at most 256 blocks per frame for k_hist_reduce. */
 constexpr unsigned kHistThreads = 256;
-unsigned hist_threads() { return g_tune[10] >= 1000 ? (unsigned)(g_tune[10] / 1000) * 256u : kHistThreads; } /* experiments: key 10 = 1000 * (threads / 256) + trips */
 unsigned hist_bpf(size_t frame_bytes, unsigned n) {
   if (g_tune[11] > 0) return (unsigned)g_tune[11];
-  const size_t bt = hist_threads();
-  const size_t chunks = frame_bytes / 16 + 1, trips = g_tune[10] % 1000 > 0 ? (size_t)(g_tune[10] % 1000) : 64 * 256 / bt;
+  const size_t bt = kHistThreads, trips = 64;
+  const size_t chunks = frame_bytes / 16 + 1;
   const size_t by_size = (chunks + bt * trips - 1) / (bt * trips);
   const size_t by_fill = std::min<size_t>(std::min<size_t>((5u * topo().cus + n - 1) / n, chunks / (bt * 16)), 256); /* 5 resident blocks per CU */
   return (unsigned)std::max<size_t>(1, std::min<size_t>(std::max(by_size, by_fill), 2048));
 }
 void launch_hist_partial(dim3 grid, hipStream_t st, const uint8_t *img, size_t frame_bytes, unsigned *partial) {
-  /* more bytes than the Infinity Cache keeps (192 MiB and up): streaming loads (k_pointwise.h); key 10 = -1: never */
-  const bool nt = (size_t)grid.y * grid.z * frame_bytes >= ((size_t)192 << 20) && g_tune[10] != -1;
-  switch (hist_threads()) {
-    case 512: GS_LAUNCH(k_hist_partial<512>, grid, dim3(512), 0, st, img, frame_bytes, partial); break;
-    case 1024: GS_LAUNCH(k_hist_partial<1024>, grid, dim3(1024), 0, st, img, frame_bytes, partial); break;
-    default:
-      if (nt) GS_LAUNCH((k_hist_partial<256, true>), grid, dim3(256), 0, st, img, frame_bytes, partial);
-      else GS_LAUNCH(k_hist_partial<256>, grid, dim3(256), 0, st, img, frame_bytes, partial);
-  }
+  /* more bytes than the Infinity Cache keeps (192 MiB and up): streaming loads (k_pointwise.h) */
+  if ((size_t)grid.y * grid.z * frame_bytes >= ((size_t)192 << 20))
+    GS_LAUNCH((k_hist_partial<kHistThreads, true>), grid, dim3(kHistThreads), 0, st, img, frame_bytes, partial);
+  else GS_LAUNCH(k_hist_partial<kHistThreads>, grid, dim3(kHistThreads), 0, st, img, frame_bytes, partial);
 }
 void launch_histogram(const uint8_t *img, size_t frame_bytes, unsigned n, unsigned *hist) {
   if (n == 0) return;
@@ -508,7 +498,7 @@ void gsh_blur_sobel_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned
   if (n == 0) return;
   const size_t fb = (size_t)w * h;
   hipStream_t st = ctx().s();
-  if (g_tune[3] == 0 && radius >= 1 && radius <= 3 && strip_ok(w, h, dst, src) && w >= 32 && h >= 3 &&
+  if (radius >= 1 && radius <= 3 && strip_ok(w, h) && h >= 3 &&
       h > 2 * radius) {
     for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
       const unsigned nn = std::min(kMaxZ, n - f0);
@@ -535,7 +525,7 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
       GS_LAUNCH(k_zero_frame, dim3((2 * w + 2 * h + 255) / 256, std::min(kMaxZ, n - f0)), dim3(256), 0,
                 st, dst + fb * f0, w, h, fb);
   };
-  if (!tmp && g_tune[3] == 0 && radius >= 1 && radius <= 3 && strip_ok16(w, h, dst, src) && w >= 32 &&
+  if (!tmp && radius >= 1 && radius <= 3 && strip_ok16(w, h, dst, src) && w >= 32 &&
       h >= 3 && h > 2 * radius) { /* every window is clipped on at most one side per axis */
     /* fused: the blurred image only ever exists in registers (1 R + 1 W per pixel).
      * The fused kernel is VALU-bound (~40 % of HBM peak) and the passes after it HBM-bound with
@@ -625,7 +615,7 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
 #endif
     return;
   }
-  if (!tmp && g_tune[3] == 0 && radius >= 1 && radius <= 3 && strip_ok(w, h, dst, src) && w >= 32 && h >= 3 &&
+  if (!tmp && radius >= 1 && radius <= 3 && strip_ok(w, h) && h >= 3 &&
       h > 2 * radius) {
     /* ragged rows or frames at odd addresses: blur + sobel still in one pass (the fused kernel without its histogram
      * half), the histogram as a pass of its own: 5 B/px moved instead of 4, against 9 for the separate calls */
@@ -669,7 +659,7 @@ void gsh_filter_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, 
   /* strip kernel: 3x3, every partial sum within int16 (sum |k| <= 128), norm <= 256 */
   unsigned abs_sum = 0;
   for (unsigned i = 0; i < kw * kh; i++) abs_sum += (unsigned)std::abs((int)kernel_host[i]);
-  if (kw == 3 && kh == 3 && abs_sum <= 128 && norm <= 256 && strip_ok(w, h, dst, src) && w >= 32) {
+  if (kw == 3 && kh == 3 && abs_sum <= 128 && norm <= 256 && strip_ok(w, h)) {
     FilterK fk;
     for (int r = 0; r < 3; r++)
       for (int c = 0; c < 3; c++) fk.k[r][c] = ((uint32_t)(uint16_t)(int16_t)kernel_host[r * 3 + c]) * 0x10001u;
@@ -705,7 +695,7 @@ void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigne
   const size_t sfb = (size_t)sw * sh, dfb = (size_t)(sw / 2) * (sh / 2);
   for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
     const unsigned nn = std::min(kMaxZ, n - f0);
-    if (g_tune[21] == 1 ? (sw % 16 == 0 && al16(src) && al16(dst) && sfb % 16 == 0 && dfb % 8 == 0) : sw >= 16)
+    if (sw >= 16)
       GS_LAUNCH(k_downsample8, dim3(((sw / 2 + 7) / 8 + 63) / 64, (sh / 2 + 3) / 4, nn), dim3(64, 4), 0, st,
                 dst + dfb * f0, src + sfb * f0, sw, sh);
     else

@@ -5,9 +5,7 @@
  * Generic form, any w/h/alignment: (1) k_integral_rows: per-row inclusive scan (wave scan +
  * LDS carry across the 4 waves), (2) k_integral_cols: running column sums in place, coalesced
  * across columns -- 13 B/px of traffic for 5 B/px algorithmic (1 R + 4 W).  Fast path
- * (k_integral_colsum / _colbase / _band below): 6 B/px.
- *
- * k_integral_wave: barrier-free replacement of k_integral_band (one wave per band).
+ * (k_integral_colsum / _colbase / _wave below): 6 B/px.
  *
  * k_integral_pad: copies an unpadded w x h table into the (w+1) x (h+1) zero-bordered layout
  * the cascade kernel reads (turns the x>0 / y>0 guards of gs_integral_sum, ref :754-763, into
@@ -86,14 +84,11 @@ __global__ __launch_bounds__(256) void k_integral_cols(unsigned *ii, unsigned w,
   }
 }
 
-/* ---- banded form (w % 16 == 0, w <= 4096, aligned): 6 B/px instead of 13 -----------------------
+/* ---- banded form (w >= 32, any alignment): 6 B/px instead of 13 --------------------------------
  * The image is cut into bands of BH rows.  (1) k_integral_colsum: per band, the sum of every
  * column over the band's rows (reads 1 B/px, writes w u32 per band).  (2) k_integral_colbase:
- * exclusive prefix of those sums over the bands, per column (tiny).  (3) k_integral_band: one
- * 256-thread block per band spans the whole row (lane = 16 columns); it keeps the running column
- * sums V[16] in registers (starting from the band's base) and, per row, turns them into the
- * row's inclusive prefix: in-lane scan, wave scan, one LDS hand-off between the 4 waves
- * (double-buffered: one barrier per row), then writes 4 B/px once. */
+ * exclusive prefix of those sums over the bands, per column (tiny).  (3) k_integral_wave: the
+ * running column sums from the band's base on, turned into each row's inclusive prefix. */
 
 /* grid (ceil(w/4096), nbands, n frames), block 256.  Any w >= 16 and any alignment: the strip that would cross the row
  * end is anchored at w - 16 instead (it overlaps its neighbour; both store the same sums), so every load lies inside
@@ -180,53 +175,8 @@ __global__ __launch_bounds__(1024) void k_integral_colbase(unsigned *colsum, uns
   }
 }
 
-/* grid (1, nbands, n frames), block 256 */
-__global__ __launch_bounds__(256) void k_integral_band(const uint8_t *src, unsigned w, unsigned h,
-                                                       unsigned BH, unsigned nbands,
-                                                       const unsigned *colbase, unsigned *ii) {
-  __shared__ unsigned wtot[2][4];
-  const unsigned tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-  const unsigned x0 = tid * 16u;
-  const size_t fb = (size_t)w * h;
-  const BufRsrc S = make_buf(src + (size_t)blockIdx.z * fb, fb);
-  const BufRsrc D = make_buf(ii + (size_t)blockIdx.z * fb, fb * 4);
-  const unsigned y0 = blockIdx.y * BH, y1 = y0 + BH < h ? y0 + BH : h;
-  unsigned V[16];
-  {
-    const unsigned *cb = colbase + ((size_t)blockIdx.z * nbands + blockIdx.y) * w + x0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      U4 t{0, 0, 0, 0};
-      if (x0 < w) t = *(const U4 *)(cb + 4 * q);
-      V[4 * q] = t.x, V[4 * q + 1] = t.y, V[4 * q + 2] = t.z, V[4 * q + 3] = t.w;
-    }
-  }
-  U4 nxt = buf_load16(S, x0 < w ? y0 * w + x0 : kOOB);
-  for (unsigned y = y0; y < y1; y++) { /* block-uniform trip count */
-    const U4 cur = nxt;
-    nxt = buf_load16(S, (x0 < w && y + 1 < y1) ? (y + 1) * w + x0 : kOOB);
-    const uint32_t d[4] = {cur.x, cur.y, cur.z, cur.w};
-    unsigned P[16], run = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      V[k] += (d[k >> 2] >> (8 * (k & 3))) & 0xffu; /* lanes beyond w add 0 to 0 */
-      run += V[k];
-      P[k] = run;
-    }
-    const unsigned inc = wave_incl_scan(run);
-    const unsigned par = y & 1u;
-    if (lane == 63) wtot[par][wv] = inc;
-    __syncthreads();
-    unsigned off = inc - run;
-    for (unsigned q = 0; q < wv; q++) off += wtot[par][q];
-    const uint32_t ob = x0 < w ? (y * w + x0) * 4u : kOOB; /* branch-free: dropped beyond w */
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      buf_store16_wb(D, ob + 16u * q, U4{off + P[4 * q], off + P[4 * q + 1], off + P[4 * q + 2], off + P[4 * q + 3]});
-  }
-}
-
-/* Barrier-free form of step (3): one WAVE per band spans the whole row.  The row is cut into TILES
+/* Step (3), barrier-free: one WAVE per band spans the whole row (the block-per-band form it replaced, one barrier
+ * per row, has been removed).  The row is cut into TILES
  * tiles of 256 px; in tile t the lane owns the 4 px at t*256 + 4*lane, so every load is one
  * coalesced 256-B dword row per wave and every store one coalesced 1-KiB dwordx4 row.  Running
  * column sums V[TILES][4] live in registers; per row: in-lane prefix of 4, one DPP wave scan per

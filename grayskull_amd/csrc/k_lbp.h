@@ -278,7 +278,6 @@ struct LbpPhases { /* phase p = stages [end[p-1], end[p]) */
   unsigned adaptive_max;
   unsigned adaptive_tenths; /* re-pack once alive <= tenths/10 of the chunk */
   unsigned adaptive_next[3]; /* later re-packing points, in stages after the first one (0 = none) */
-  unsigned quad;             /* 1: re-packed survivors are evaluated four lanes per window (lbp_quad_stages) */
   /* k_lbp_tile (k_lbp_tile.h): a WAVE runs its windows densely through stages [0, tile_first) and then stage by stage while more
    * than tile_tenths/10 of them are alive (and fewer than adaptive_max stages are done); after that one lane per (window,
    * classifier) pair.  A pair costs about twice a dense lane-evaluation, so the switch pays from half the windows dead:
@@ -430,7 +429,7 @@ __global__ __launch_bounds__(256) void k_lbp_cascade(LbpArgs a, LbpPhases ph) {
     const bool lastp = p + 1 == np;
     const uint16_t *qin = queue + cur * kChunkItems;
     uint16_t *qout = queue + (cur ^ 1u) * kChunkItems;
-    if (ph.quad && p > 0u) { /* re-packed survivors: a quad of lanes per window, 64 windows per block iteration */
+    if (p > 0u) { /* re-packed survivors: a quad of lanes per window, 64 windows per block iteration */
       for (unsigned i0 = 0; i0 < n_in; i0 += 64u) { /* block-uniform trip count */
         const unsigned i = i0 + (tid >> 2), ci = tid & 3u;
         const bool live = i < n_in;
@@ -453,12 +452,12 @@ __global__ __launch_bounds__(256) void k_lbp_cascade(LbpArgs a, LbpPhases ph) {
         }
       }
     } else
-    for (unsigned i0 = 0; i0 < n_in; i0 += 256u) { /* block-uniform trip count */
+    for (unsigned i0 = 0; i0 < n_in; i0 += 256u) { /* block-uniform trip count; phase 0: every window of the chunk */
       const unsigned i = i0 + tid;
       bool pass = false;
       unsigned local = 0;
       if (i < n_in) {
-        local = p ? qin[i] : i;
+        local = i;
         pass = lbp_window_stages<GUARD, COUNT>(t, Pg, lbp_origin(a, sc, first + local), a.limit_bytes, s0, s1, &evals);
       }
       if (lastp) {

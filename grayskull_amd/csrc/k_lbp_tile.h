@@ -255,9 +255,6 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 8 : 1) void k_lbp_tile(LbpArgs a, 
     const unsigned per = (ntiles + 7u) >> 3, j = blockIdx.x >> 3;
     if (j >= per) return;
     tix = (blockIdx.x & 7u) * per + j;
-  } else if (a.xcd_swizzle >= 16u) { /* experiments: runs of G = xcd_swizzle - 16 tiles dealt round the XCDs */
-    const unsigned G = a.xcd_swizzle - 16u, j = blockIdx.x >> 3;
-    tix = ((j / G) * 8u + (blockIdx.x & 7u)) * G + j % G;
   }
   if (tix >= ntiles) return; /* whole block */
   const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;

@@ -37,40 +37,42 @@ void gsh_sync(void);                      /* hipStreamSynchronize(current stream
  * atomic; nothing in a product path writes them): measurement scripts and the test-suite use it to force the paths a
  * heuristic would not take on a given input.  RESULTS NEVER DEPEND ON ANY KEY.  (The two probes that did change results --
  * the cascade without rect emission, gs_sobel without its column reads -- exist only in builds with -DGS_EXPERIMENT, see
- * below.)  0 is every key's default. */
+ * below.)  0 is every key's default.  A RETIRED key or value forced a path that has since been removed; gsh_tune ignores it
+ * (one line on stderr), and its number is never reused: the logs under profiles/ cite it. */
 enum gsh_tune_key {
   GSH_TUNE_STRIP_BAND_ROWS = 0,   /* rows per band of the strip kernels (0 = auto) */
-  GSH_TUNE_STRIP_BLOCK_SHAPE = 1, /* 0: 64x4, 1: 256x1, 2: 128x2, 3: by frame width (default) */
-  GSH_TUNE_2 = 2,                 /* reserved (default 1) */
-  GSH_TUNE_NO_FUSED_PIPELINE = 3, /* 1: gsh_edge_pipeline_batch on the separate per-call kernels */
+  GSH_TUNE_STRIP_BLOCK_SHAPE = 1, /* 0: by frame width (default), 1: 64x4, 2: 128x2, 3: 256x1 */
+  GSH_TUNE_RETIRED_2 = 2,         /* retired */
+  GSH_TUNE_RETIRED_3 = 3,         /* retired (gsh_edge_pipeline_batch forced onto the separate per-call kernels) */
   GSH_TUNE_LBP_PHASE_PRESET = 4,  /* k_lbp_cascade: preset of the stages at which a block re-packs survivors (1: never; >= 1000: custom split) */
   GSH_TUNE_PIPELINE_CHUNK = 5,    /* frames per chunk of gsh_edge_pipeline_batch's internal overlap (0 = 32, negative = never split) */
-  GSH_TUNE_COMPARE = 6,           /* 1 generic two-pass gs_integral, 2 block-per-band gs_integral, 3 integral-image route for gs_blur(r > 3) /
-                                     gs_adaptive_threshold, 4 the any-radius box kernel also for radii <= 16, 5 ... for ragged rows only, 6 / 7 k_box_edge always on the caller's / on the side stream,
-                                     8 gs_integral without the streaming loads of batches beyond the Infinity Cache */
+  GSH_TUNE_COMPARE = 6,           /* 3 integral-image route for gs_blur(r > 3) / gs_adaptive_threshold, 4 the any-radius box kernel also for
+                                     radii <= 16, 7 k_box_edge always on the side stream, 8 gs_integral without the streaming loads of
+                                     batches beyond the Infinity Cache (1, 2, 5, 6 retired) */
   GSH_TUNE_FAST_SCORE = 7,        /* 0: k_fast_score_q4 (LDS tile, candidates queued), 2: k_fast_score_px (one global byte load per ring pixel) */
   GSH_TUNE_FRAMES_PER_LAUNCH = 8, /* test hook for the batch splitting of every launcher */
   GSH_TUNE_LBP_ADAPTIVE = 9,      /* k_lbp_cascade: max stages + 16 * tenths [+ later points] of the first re-packing point */
-  GSH_TUNE_HIST_TRIPS = 10,       /* trips per block gs_histogram aims at; -1: default-policy loads also for batches beyond the Infinity Cache (A/B) */
-  GSH_TUNE_HIST_BLOCKS = 11,      /* its blocks per frame */
+  GSH_TUNE_RETIRED_10 = 10,       /* retired (gs_histogram's trips per block, block size and load policy) */
+  GSH_TUNE_HIST_BLOCKS = 11,      /* blocks per frame of gs_histogram (test hook: several blocks on small frames) */
   GSH_TUNE_HIST_PIECE = 12,       /* bytes per histogram piece (test hook for images above 1 GiB) */
-  GSH_TUNE_LBP_XCD = 13,          /* chunk / tile -> XCD mapping of the LBP kernels: 1 dispatch order, 2 XCD-aware always (0: k_lbp_cascade by table size, k_lbp_tile in dispatch order) */
+  GSH_TUNE_LBP_XCD = 13,          /* chunk / tile -> XCD mapping of the LBP kernels: 1 dispatch order, 2 XCD-aware always (0: k_lbp_cascade
+                                     by table size, k_lbp_tile in dispatch order; >= 3 retired) */
   GSH_TUNE_LBP_KERNEL = 14,       /* 0: per scale by rule (k_lbp_tile with the tile shape the scale's LDS footprint allows, else
-                                     k_lbp_cascade), 1: k_lbp_cascade for every scale, -1: the rule without its one-block-per-CU
-                                     fallback, 2 + i: tile shape i of k_lbp_tile wherever it fits */
+                                     k_lbp_cascade), 1: k_lbp_cascade for every scale, 2 + i: tile shape i (0..2) of k_lbp_tile wherever
+                                     it fits (-1, 5, 6 retired) */
   GSH_TUNE_LBP_TILE_SWITCH = 15,  /* k_lbp_tile: first + 16 * tenths -- dense stages [0, first), then while more than tenths/10 of a
                                      wave's windows live, then one lane per (window, classifier) pair */
   GSH_TUNE_EXPERIMENT_16 = 16,    /* GS_EXPERIMENT builds only: gs_lbp_detect runs its kernels but emits nothing */
-  GSH_TUNE_LBP_ONE_LANE = 17,     /* 1: k_lbp_cascade evaluates re-packed windows one per lane instead of one per quad */
+  GSH_TUNE_RETIRED_17 = 17,       /* retired (k_lbp_cascade's one lane per re-packed window) */
   GSH_TUNE_STRIP_XCD = 18,        /* band -> XCD mapping of the strip kernels / tile -> XCD mapping of the gs_fast score pass: 1 dispatch
                                      order, 2 XCD-aware always */
   GSH_TUNE_FAST_NMS = 19,         /* 0: k_fast_nms_sparse behind the score kernel's bitmap, 1: k_fast_nms item by item */
   GSH_TUNE_TMATCH = 20,           /* 1: gs_match_template on the VALU dot-product kernels; 2 / 3: matrix-core kernel with 64 x 128 / 32 x 64
                                      tiles whatever the image size; 4 / 5: window sums of squares always by passes / always from the table */
-  GSH_TUNE_STRIP_ROUND3_RULE = 21,/* 1: strip kernels only for whole 16-px strips at 16-byte aligned addresses */
+  GSH_TUNE_RETIRED_21 = 21,       /* retired (round 3's rule for the strip kernels) */
   GSH_TUNE_EXPERIMENT_22 = 22,    /* GS_EXPERIMENT builds only: gs_sobel without the reads that preserve columns 0 / w-1 */
   GSH_TUNE_EXPERIMENT_23 = 23,    /* GS_EXPERIMENT builds only: the strip-copy probe keeps the stencils' halo load */
-  GSH_TUNE_STRIP_REALIGN = 24     /* realigning strip flavour: 1 never, 2 always, 0 by address phase and width */
+  GSH_TUNE_RETIRED_24 = 24        /* retired (realigning strip flavour never / always) */
 };
 void gsh_tune(int key, int value);
 /* measurement aid for bench.py: while on, gsh_edge_pipeline_batch brackets every launch of its

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 g = gs.Grayskull(os.environ["UB_LIB"]) if os.environ.get("UB_LIB") else gs.lib(); g.use_torch_stream()
 casc = Cascade.from_blob(os.path.join(ROOT, "tests/golden/frontalface_cascade.bin"))
 dc = g.cascade_create(casc)
-SHAPES = {1: "k_lbp_cascade", 2: "tile 512thr 128x32", 3: "tile 1024thr 128x32", 4: "tile 1024thr 64x32", 5: "tile 1024thr 64x16", 6: "tile 512thr 64x32", 0: "rule"}
+SHAPES = {1: "k_lbp_cascade", 2: "tile 512thr 128x32", 3: "tile 1024thr 128x32", 4: "tile 1024thr 64x32", 0: "rule"}
 def timeit(fn, reps=3):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     fn(); torch.cuda.synchronize(); e0.record()
@@ -36,7 +36,7 @@ for (kind, w, h, n) in (("edges", 3840, 2160, 8), ("noise", 1920, 1080, 8), ("no
         if key not in ref: ref[key] = (c, rects.clone())
         return c == ref[key][0] and bool((rects == ref[key][1]).all())
     for rnd in range(2):
-        for mode in (1, 2, 3, 4, 5, 6, 0):
+        for mode in (1, 2, 3, 4, 0):
             g.tune(14, mode)
             ms = timeit(run)
             print("%s %dx%d whole scan, %-22s %.3f ms/frame  same=%s" % (kind, w, h, SHAPES[mode] + ":", ms / n, check("all")), flush=True)
@@ -51,7 +51,7 @@ for (kind, w, h, n) in (("edges", 3840, 2160, 8), ("noise", 1920, 1080, 8), ("no
     s = 1.0
     while s <= 4.0:
         line = "%s %dx%d scale %.3f:" % (kind, w, h, s)
-        for mode in (1, 2, 3, 4, 5, 6):
+        for mode in (1, 2, 3, 4):
             g.tune(14, mode)
             ms = timeit(lambda: run(s, s * 1.05))
             line += "  %s %.3f%s" % (SHAPES[mode].replace("tile ", "").replace("k_lbp_", ""), ms / n, "" if check("s%.3f" % s) else " DIFF")

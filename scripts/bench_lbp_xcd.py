@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""chunk / tile -> XCD mapping of the LBP kernels (gsh_tune key 13: 0 = the rule, 1 = dispatch order, 2 = eighths always, 3 = tile rows dealt
-round the XCDs [k_lbp_cascade: eighths], 4 = tiles in dispatch order [k_lbp_cascade: eighths]) with the rule's kernels: 8 frames of
-edge maps and of block noise at 4K, 1440p, 1080p, 720p.  (First version of this script, profiles/r05j_lbp_xcd.log: keys 0 1 2 with
+"""chunk / tile -> XCD mapping of the LBP kernels (gsh_tune key 13: 0 = the rule, 1 = dispatch order, 2 = eighths always) with the
+rule's kernels: 8 frames of edge maps and of block noise at 4K, 1440p, 1080p, 720p; PER_SCALE=1: eighths against the rule (at 4K and
+1440p: tiles in dispatch order, k_lbp_cascade in eighths) one scale at a time.  (First version of this script, profiles/r05j_lbp_xcd.log: keys 0 1 2 with
 the rule and with k_lbp_cascade for every scale.)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,7 +35,7 @@ for (kind, w, h, n) in (("edges", 3840, 2160, 8), ("noise", 3840, 2160, 8), ("ed
         s = 1.0
         while s <= 4.0:
             line = "%s %dx%d scale %.3f:" % (kind, w, h, s)
-            for k13 in (2, 4, 2, 4):
+            for k13 in (2, 0, 2, 0):
                 g.tune(13, k13)
                 ms = timeit(lambda: g.lbp_detect_batch(dc, ii, rects, counts, 4096, 1.1, s, s * 1.05, 1))
                 line += "  key 13 = %d %.4f" % (k13, ms / n)

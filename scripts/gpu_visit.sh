@@ -17,8 +17,8 @@
 #   lbppmc       counters of the LBP kernels on the configs[4] input: the rule and k_lbp_cascade
 #   fast         scripts/ubench_fast.py (flat / block noise / lena / random)
 #   fastpmc      SQ_INSTS_VALU of the gs_fast passes -> profiles/fast_valu_pmc.json workflow
-#   extras       ragged shapes, box offsets, next rows, template matching micro-benchmarks
-#   boxragged    scripts/ubench_box_ragged.py (sliding box on ragged / aligned batches, k_box_edge on the side / the caller's stream) + its kernels under rocprofv3
+#   extras       box offsets, next rows, template matching micro-benchmarks
+#   boxragged    scripts/ubench_box_ragged.py (sliding box on ragged / aligned batches) + its kernels under rocprofv3
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R; mkdir -p gpurun_out; export TMPDIR=/tmp
 TAG=${1:?usage: gpu_visit.sh TAG section...}; shift
@@ -70,7 +70,6 @@ for sec in "$@"; do
       python scripts/pmc_fast_json.py > ${O}_pmc_fast_json.log 2>&1; tail -2 ${O}_pmc_fast_json.log | cut -c1-300 ;;
     extras)
       export UB_LIB=$R/build_variants/libgs_experiment.so  # the strip-copy probe lives in experiment builds only
-      RG_CHECK=0 timeout 500 python scripts/ubench_ragged.py 2>&1 | grep -v amdgpu.ids | tee ${O}_ragged.log | tail -40
       timeout 300 python scripts/ubench_box_offsets.py 2>&1 | grep -v amdgpu.ids | tee ${O}_box_offsets.log
       timeout 300 python scripts/ubench_next_rows.py 2>&1 | grep -v amdgpu.ids | tee ${O}_next_rows.log | tail -12
       timeout 300 python scripts/ubench_tmatch.py 2>&1 | grep -v amdgpu.ids | tee ${O}_tmatch.log | tail -12

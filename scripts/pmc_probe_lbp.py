@@ -15,7 +15,6 @@ ii = torch.zeros((n, h, w), dtype=torch.int32, device="cuda"); g.integral_batch(
 dc = g.cascade_create(Cascade.from_blob(os.path.join(ROOT, "tests/golden/frontalface_cascade.bin")))
 rects = torch.zeros((n, 4096, 4), dtype=torch.int32, device="cuda"); counts = torch.zeros(n, dtype=torch.int32, device="cuda")
 g.tune(14, int(os.environ.get("LBP_MODE", 0)))
-if os.environ.get("LBP_ONE_LANE") == "1": g.tune(17, 1)  # one lane per re-packed window (round-2 survivors)
 for _ in range(2):
     g.lbp_detect_batch(dc, ii, rects, counts, 4096, 1.1, 1.0, 4.0, 1)
 torch.cuda.synchronize()

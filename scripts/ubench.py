@@ -25,21 +25,20 @@ ops = {"copy": lambda: g.probe_strip_copy(dst, src), "erode": lambda: g.erode_ba
        "blur1": lambda: g.blur_batch(dst, src, 1), "blur3": lambda: g.blur_batch(dst, src, 3)}
 which = os.environ.get("UB_OPS", "copy,erode,sobel,blur2").split(",")
 Ts = [int(x) for x in os.environ.get("UB_T", "0,16,32,64,128,270").split(",")]
-geoms = [int(x) for x in os.environ.get("UB_G", "0,1,2").split(",")]
-pfs = [int(x) for x in os.environ.get("UB_PF", "1,2,3").split(",")]
+geoms = [int(x) for x in os.environ.get("UB_G", "1,2,3").split(",")]  # gsh_tune key 1: 0 by width, 1 64x4, 2 128x2, 3 256x1
 res = {}
 for rnd in range(3):
     for op in which:
-        for T, gm, pf in itertools.product(Ts, geoms, pfs):
-            g.tune(0, T); g.tune(1, gm); g.tune(2, pf)
-            res.setdefault((op, T, gm, pf), []).append(timeit(ops[op], 5))
-print("%-6s %4s %2s %2s %9s %8s %6s" % ("op", "T", "g", "pf", "ms(med)", "GB/s", "frac"))
+        for T, gm in itertools.product(Ts, geoms):
+            g.tune(0, T); g.tune(1, gm)
+            res.setdefault((op, T, gm), []).append(timeit(ops[op], 5))
+print("%-6s %4s %2s %9s %8s %6s" % ("op", "T", "g", "ms(med)", "GB/s", "frac"))
 best = {}
-for (op, T, gm, pf), v in sorted(res.items()):
+for (op, T, gm), v in sorted(res.items()):
     ms = float(np.median(v)); gbs = 2.0 * npx / ms / 1e6
-    print("%-6s %4d %2d %2d %9.4f %8.1f %6.3f" % (op, T, gm, pf, ms, gbs, gbs / 8000))
-    if op not in best or ms < best[op][0]: best[op] = (ms, T, gm, pf, gbs)
-print("BEST", json.dumps({k: {"ms": round(v[0], 4), "T": v[1], "geom": v[2], "pf": v[3], "GB/s": round(v[4], 1)} for k, v in best.items()}))
+    print("%-6s %4d %2d %9.4f %8.1f %6.3f" % (op, T, gm, ms, gbs, gbs / 8000))
+    if op not in best or ms < best[op][0]: best[op] = (ms, T, gm, gbs)
+print("BEST", json.dumps({k: {"ms": round(v[0], 4), "T": v[1], "geom": v[2], "GB/s": round(v[3], 1)} for k, v in best.items()}))
 # reference points: plain streaming kernels
 t = timeit(lambda: g.threshold_batch(dst, 100)); print("threshold(in place) GB/s %.1f" % (2.0 * npx / t / 1e6))
 t = timeit(lambda: dst.copy_(src)); print("torch copy_ GB/s %.1f" % (2.0 * npx / t / 1e6))

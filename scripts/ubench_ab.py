@@ -32,7 +32,7 @@ for rnd in range(int(os.environ.get("AB_ROUNDS", 5))):
     for op in ops:
         for T in Ts:
             for t in tags:
-                g = libs[t]; g.tune(0, T); g.tune(1, int(os.environ.get("UB_G", 1)))
+                g = libs[t]; g.tune(0, T); g.tune(1, int(os.environ.get("UB_G", 3)))  # gsh_tune key 1 = 3: 256x1 blocks
                 res.setdefault((op, T, t), []).append(timeit(call(g, op)))
 print("%-6s %4s %-10s %9s %9s %8s" % ("op", "T", "variant", "ms(med)", "ms(min)", "GB/s"))
 for (op, T, t), v in sorted(res.items()):

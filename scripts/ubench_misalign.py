@@ -6,7 +6,6 @@ import numpy as np, torch
 import grayskull_amd as gs
 g = gs.Grayskull(os.environ["UB_LIB"]) if os.environ.get("UB_LIB") else gs.lib()
 g.use_torch_stream()
-if os.environ.get("UB_TUNE24"): g.tune(24, int(os.environ["UB_TUNE24"]))
 W, H, F = 3840, 2160, 64
 def timeit(fn, reps=10):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -318,17 +318,22 @@ def test_batch_entry_points(emu, oracle):
         assert sums[i] == np.sum(idx * (gen[i].reshape(-1).astype(np.uint64) + 1), dtype=np.uint64)
 
 
+# geom: block shape 64 x 4, 256 x 1, 128 x 2 (gsh_tune key 1 = 1, 3, 2); frame: one of three frame shapes
+STRIP_GEOM_KEY = (1, 3, 2)
+STRIP_FRAMES = {1: (2064, 11), 2: (64, 23), 3: (4112, 4)}
+
+
 @pytest.mark.parametrize("geom", [0, 1, 2])
-@pytest.mark.parametrize("pf", [1, 2, 3])
-def test_strip_launch_tuning_never_changes_results(emu, oracle, geom, pf):
-    """gsh_tune: block shape x prefetch depth x rows-per-band, incl. bands of 1 row"""
+@pytest.mark.parametrize("frame", [1, 2, 3])
+def test_strip_launch_tuning_never_changes_results(emu, oracle, geom, frame):
+    """gsh_tune: block shape x rows-per-band, incl. bands of 1 row"""
+    w, h = STRIP_FRAMES[frame]
     try:
         for T in (0, 1, 5):
-            emu.tune(0, T), emu.tune(1, geom), emu.tune(2, pf)
-            for (w, h) in ((2064, 11), (64, 23), (4112, 4)):
-                pc.stencils(emu, oracle, Oracle.synth(w, h, w + h + T), MEM, radii=(1, 2, 3))
+            emu.tune(0, T), emu.tune(1, STRIP_GEOM_KEY[geom])
+            pc.stencils(emu, oracle, Oracle.synth(w, h, w + h + T), MEM, radii=(1, 2, 3))
     finally:
-        emu.tune(0, 0), emu.tune(1, 3), emu.tune(2, 2)
+        emu.tune(0, 0), emu.tune(1, 0)
 
 
 @pytest.mark.parametrize("radius", [1, 2, 3])
@@ -444,7 +449,7 @@ def test_lbp_cap_reached_in_early_scales(emu, oracle, cascade):
     pc.lbp(emu, oracle, Oracle.synth(64, 48, 9), MEM, random_cascade(1), params=((3, 1.25, 1.0, 2.0, 1), (200, 1.1, 1.0, 2.0, 1)))
 
 
-@pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, 6])
+@pytest.mark.parametrize("mode", [1, 2, 3, 4])
 def test_lbp_tile_shapes_never_change_results(emu, oracle, cascade, mode):
     """key 14: 1 = k_lbp_cascade for every scale, 2 + i = tile shape i of k_lbp_tile (k_lbp_tile.h: corners from an LDS tile,
     per-wave dense phase, survivors one lane per (window, classifier) pair) wherever its tile fits -- partial tiles at the
@@ -685,7 +690,7 @@ def test_histogram_of_an_image_larger_than_one_launch_frame(emu, oracle):
         emu.tune(12, 0)
 
 
-@pytest.mark.parametrize("mode", [1, 2, 19])
+@pytest.mark.parametrize("mode", [1, 2])
 def test_lbp_chunk_to_xcd_mapping_never_changes_results(emu, oracle, cascade, mode):
     """gsh_tune key 13: 1 = chunks in dispatch order, 2 = XCD-aware mapping (chunk = (block % 8) * ceil(nchunks / 8) + block / 8,
     grid padded to a multiple of 8) -- forced on small images: scales with 1, 7, 9 and a few dozen chunks, caps reached early"""
