@@ -17,13 +17,14 @@ import os
 
 import numpy as np
 
-from ._abi import (GsImage, GsLbpCascade, GsPoint, GsRect, KEYPOINT_DTYPE, MATCH_DTYPE, RECT_DTYPE)
+from ._abi import (BLOB_DTYPE, GsImage, GsLbpCascade, GsPoint, GsRect, KEYPOINT_DTYPE, MATCH_DTYPE, POINT_DTYPE,
+                   RECT_DTYPE)
 from .cascade import Cascade
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIBRARY = os.path.join(_HERE, "libgrayskull_hip.so")
 
-__all__ = ["Grayskull", "Cascade", "lib", "KEYPOINT_DTYPE", "MATCH_DTYPE", "RECT_DTYPE"]
+__all__ = ["Grayskull", "Cascade", "lib", "BLOB_DTYPE", "KEYPOINT_DTYPE", "MATCH_DTYPE", "POINT_DTYPE", "RECT_DTYPE"]
 
 
 def _ptr(a):
@@ -82,6 +83,9 @@ _SIGS = {
     "gs_resize": (None, [GsImage, GsImage]),
     "gs_match_template": (None, [GsImage, GsImage, GsImage]),
     "gs_find_best_match": (GsPoint, [GsImage]),
+    "gs_blobs": (C.c_uint, [GsImage, C.c_void_p, C.c_void_p, C.c_uint]),
+    "gs_blob_corners": (None, [GsImage, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_perspective_correct": (None, [GsImage, GsImage, C.c_void_p]),
     # runtime + batch (include/grayskull_hip.h)
     "gsh_version": (C.c_char_p, []),
     "gsh_device_count": (C.c_int, []),
@@ -141,6 +145,12 @@ _SIGS = {
     "gsh_filter_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
                                 C.c_uint, C.c_uint, C.c_uint]),
     "gsh_downsample_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_blobs_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_uint]),
+    "gsh_blob_corners_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
+                                       C.c_void_p]),
+    "gsh_perspective_correct_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint,
+                                              C.c_uint, C.c_void_p]),
     "gsh_synth_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint32]),
     "gsh_checksum_batch": (None, [C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),
     # multi-GPU control plane of one-process host programs (csrc/gs_comm.cpp; RCCL looked up at run time)
@@ -316,6 +326,27 @@ class Grayskull:
     def find_best_match(self, result):  # grayskull.h:726
         p = self.c.gs_find_best_match(_img(result))
         return int(p.x), int(p.y)
+
+    def blobs(self, img, nblobs, labels=None):
+        """grayskull.h:330 -> (BLOB_DTYPE records of the m blobs, labels).  `labels` (h, w) uint16 may be a device
+        tensor (zero-copy); by default a host array is allocated and returned."""
+        if labels is None:
+            labels = np.zeros(img.shape, np.uint16)
+        recs = np.zeros(max(nblobs, 1), BLOB_DTYPE)
+        m = self.c.gs_blobs(_img(img), _ptr(labels), recs.ctypes.data, nblobs)
+        return recs[:m].copy(), labels
+
+    def blob_corners(self, img, labels, blob):
+        """grayskull.h:404: blob is one BLOB_DTYPE record -> [(x, y)] * 4 in the order tl, tr, br, bl"""
+        b = np.ascontiguousarray(np.asarray(blob, BLOB_DTYPE).reshape(1))
+        c = np.zeros(4, POINT_DTYPE)
+        self.c.gs_blob_corners(_img(img), _ptr(labels), b.ctypes.data, c.ctypes.data)
+        return [(int(p["x"]), int(p["y"])) for p in c]
+
+    def perspective_correct(self, dst, src, corners):
+        """grayskull.h:423: corners = 4 (x, y) pairs tl, tr, br, bl"""
+        c = np.ascontiguousarray(np.asarray(corners, np.uint32).reshape(4, 2))
+        self.c.gs_perspective_correct(_img(dst), _img(src), c.ctypes.data)
 
     def integral(self, src, ii=None):  # grayskull.h:744
         if ii is None:
@@ -503,6 +534,23 @@ class Grayskull:
     def downsample_batch(self, dst, src):
         n, h, w = self._nhw(src)
         self.c.gsh_downsample_batch(_ptr(dst), _ptr(src), w, h, n)
+
+    def blobs_batch(self, img, labels, blobs, counts, nblobs):
+        """gsh_blobs_batch: img (n, h, w) uint8, labels (n, h, w) uint16 [or int16], blobs (n, nblobs, 8) int32 (one
+        32-byte record per row: see BLOB_DTYPE), counts (n) int32 -- all device tensors; stream-ordered"""
+        n, h, w = self._nhw(img)
+        self.c.gsh_blobs_batch(_ptr(img), w, h, n, _ptr(labels), _ptr(blobs), _ptr(counts), nblobs)
+
+    def blob_corners_batch(self, img, labels, blobs, corners):
+        """gsh_blob_corners_batch: blobs (n, 8) int32 -- one record per frame --, corners (n, 4, 2) int32"""
+        n, h, w = self._nhw(img)
+        self.c.gsh_blob_corners_batch(_ptr(img), _ptr(labels), w, h, n, _ptr(blobs), _ptr(corners))
+
+    def perspective_correct_batch(self, dst, src, corners):
+        """gsh_perspective_correct_batch: dst (n, dh, dw), src (n, sh, sw) uint8, corners (n, 4, 2) int32"""
+        n, sh, sw = self._nhw(src)
+        _, dh, dw = self._nhw(dst)
+        self.c.gsh_perspective_correct_batch(_ptr(dst), dw, dh, _ptr(src), sw, sh, n, _ptr(corners))
 
     def synth_batch(self, dst, seed0):
         n, h, w = self._nhw(dst)

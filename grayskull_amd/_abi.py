@@ -1,7 +1,7 @@
 """ctypes / numpy mirrors of the reference's C structs (grayskull.h:14-64).
 
 Layouts are the x86-64 SysV ones the reference compiles to:
-gs_image 16 B, gs_rect 16 B, gs_point 8 B, gs_keypoint 48 B, gs_match 12 B,
+gs_image 16 B, gs_rect 16 B, gs_point 8 B, gs_blob 32 B, gs_keypoint 48 B, gs_match 12 B,
 gs_lbp_cascade 96 B.  Checked by tests/test_abi.py against the C headers.
 """
 import ctypes as C
@@ -19,6 +19,10 @@ class GsRect(C.Structure):  # grayskull.h:19-21
 
 class GsPoint(C.Structure):  # grayskull.h:23-25
     _fields_ = [("x", C.c_uint), ("y", C.c_uint)]
+
+
+class GsBlob(C.Structure):  # grayskull.h:29-34 (gs_label is u16, 2 bytes of padding follow it)
+    _fields_ = [("label", C.c_uint16), ("area", C.c_uint), ("box", GsRect), ("centroid", GsPoint)]
 
 
 class GsKeypoint(C.Structure):  # grayskull.h:42-47
@@ -43,9 +47,13 @@ class GsLbpCascade(C.Structure):  # grayskull.h:54-64
 KEYPOINT_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("response", "<u4"), ("angle", "<f4"),
                            ("desc", "<u4", (8,))])
 RECT_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("w", "<u4"), ("h", "<u4")])
+BLOB_DTYPE = np.dtype([("label", "<u2"), ("pad", "<u2"), ("area", "<u4"), ("x", "<u4"), ("y", "<u4"), ("w", "<u4"),
+                       ("h", "<u4"), ("cx", "<u4"), ("cy", "<u4")])
+POINT_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4")])
 MATCH_DTYPE = np.dtype([("idx1", "<u4"), ("idx2", "<u4"), ("distance", "<u4")])
 
 assert C.sizeof(GsImage) == 16 and C.sizeof(GsRect) == 16 and C.sizeof(GsPoint) == 8
 assert C.sizeof(GsKeypoint) == 48 == KEYPOINT_DTYPE.itemsize
 assert C.sizeof(GsMatch) == 12 == MATCH_DTYPE.itemsize
+assert C.sizeof(GsBlob) == 32 == BLOB_DTYPE.itemsize and POINT_DTYPE.itemsize == 8
 assert C.sizeof(GsLbpCascade) == 96 and RECT_DTYPE.itemsize == 16

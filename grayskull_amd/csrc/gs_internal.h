@@ -8,6 +8,7 @@
  *   gs_detect.cpp   ordered compaction, FAST, LBP cascade, ORB, matching (+ their C ABI)
  *   gs_comm.cpp     RCCL control plane for one-process multi-GPU host programs
  *   gs_fused.cpp, gs_box.cpp  kernels with their own compiler flags
+ *   gs_blobs.cpp    connected components, blob corners, perspective correction (+ their C ABI)
  *
  * libgrayskull_hip.so: host runtime and C-ABI.
  *
@@ -80,7 +81,8 @@ namespace gsi {
 /* ------------------------------------------------------------------ per-thread context */
 enum Slot { SL_IN = 0, SL_OUT, SL_AUX, SL_AUX2, SL_II, SL_PAD, SL_MASK, SL_CNT, SL_PFX, SL_TOT, SL_PRE,
             SL_HISTP, SL_HIST, SL_THR, SL_KPS, SL_MOM, SL_KIN, SL_DESC, SL_TAB, SL_JUMP, SL_LEV,
-            SL_BEST, SL_NZ, SL_COUNT };
+            SL_BEST, SL_NZ,
+            SL_BLOB_BITS, SL_BLOB_PAR, SL_BLOB_STAT, SL_BLOB_ROW, SL_BLOB_LAB, SL_BLOB_REC, SL_COUNT }; /* gs_blobs.cpp */
 
 /* gsh_edge_pipeline_batch: frames per chunk (measured best for 64..512-frame batches of 4K frames:
  * profiles/r01g_chunk_overlap.log) and the most chunks per call */

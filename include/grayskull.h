@@ -19,8 +19,8 @@
  *     calling thread's stream (see grayskull_hip.h), synchronised before return
  *     unless gsh_set_async(1).
  *
- * Out of scope here (not on the hot path): gs_blobs, contours,
- * perspective correction, PGM I/O, gs_alloc / gs_free.  Callers that need them
+ * Out of scope here: contours (gs_trace_contour, one sequential
+ * walk per contour), PGM I/O, gs_alloc / gs_free.  Callers that need them
  * include the reference header for those functions.
  */
 #ifndef GRAYSKULL_H
@@ -48,6 +48,13 @@ extern "C" {
 struct gs_image { unsigned w, h; uint8_t *data; };                 /* 16 B, ref :14-17 */
 struct gs_rect { unsigned x, y, w, h; };                           /* 16 B, ref :19-21 */
 struct gs_point { unsigned x, y; };                                /*  8 B, ref :23-25 */
+typedef uint16_t gs_label;                                         /*        ref :27    */
+struct gs_blob {                                                   /* 32 B, ref :29-34 */
+  gs_label label;
+  unsigned area;
+  struct gs_rect box;
+  struct gs_point centroid;
+};
 struct gs_keypoint {                                               /* 48 B, ref :42-47 */
   struct gs_point pt;
   unsigned response;
@@ -165,6 +172,21 @@ GS_API void gs_resize(struct gs_image dst, struct gs_image src);                
 GS_API void gs_match_template(struct gs_image img, struct gs_image tmpl,
                               struct gs_image result);                          /* ref :705 */
 GS_API struct gs_point gs_find_best_match(struct gs_image result);              /* ref :726 */
+
+/* ---- connected components and what the reference builds on them (docs/design/blobs.md) ----------
+ * gs_blobs: 4-connected components of img >= 128, labelled and numbered exactly like the reference, its
+ * "out of labels" behaviour past nblobs start pixels included.  Returns m after a sync; records [0, m) are
+ * written, records [m, nblobs) are left as they were (the reference leaves stale provisional data there).
+ * gs_label is u16, so at most 65535 labels are handed out whatever nblobs says.  With nblobs >= 65535
+ * and 65535 or more start pixels the reference's u16 label counter wraps to 0: with exactly 65535 it
+ * returns 0 (labels written, no records), with more it writes blobs[-1] (undefined).  The library returns
+ * 0 in both cases, with the labels written as if nblobs were 65535 and no records. */
+GS_API unsigned gs_blobs(struct gs_image img, gs_label *labels, struct gs_blob *blobs,
+                         unsigned nblobs);                                      /* ref :330 */
+GS_API void gs_blob_corners(struct gs_image img, gs_label *labels, struct gs_blob *b,
+                            struct gs_point c[4]);                              /* ref :404 */
+GS_API void gs_perspective_correct(struct gs_image dst, struct gs_image src,
+                                   struct gs_point c[4]);                       /* ref :423, float32 bilinear */
 
 /* 3x3 kernels for gs_filter, as the reference spells them (ref :249-253) */
 #define gs_sharpen ((struct gs_image){3, 3, (uint8_t[]){0, -1, 0, -1, 5, -1, 0, -1, 0}})

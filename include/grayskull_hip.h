@@ -208,6 +208,20 @@ void gsh_filter_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, 
                       const int8_t *kernel_host, unsigned kw, unsigned kh, unsigned norm);
 void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n);
 
+/* ---- connected components, blob corners, perspective correction (ref :330, :404, :423) ----------
+ * The reference's document-scanner chain (blur -> Otsu threshold -> gs_blobs -> largest blob ->
+ * gs_blob_corners -> gs_perspective_correct) on n same-size frames without a host round trip.
+ * labels: n x w x h; blobs: n x nblobs records, frame f's first counts[f] written (the rest untouched);
+ * counts: n.  Corners: blobs holds ONE record per frame (e.g. each frame's largest), corners n x 4
+ * points {tl, tr, br, bl}; perspective: dst n x dw x dh from src n x sw x sh and n x 4 corners. */
+void gsh_blobs_batch(const uint8_t *img, unsigned w, unsigned h, unsigned n, gs_label *labels,
+                     struct gs_blob *blobs, unsigned *counts, unsigned nblobs);
+void gsh_blob_corners_batch(const uint8_t *img, const gs_label *labels, unsigned w, unsigned h,
+                            unsigned n, const struct gs_blob *blobs, struct gs_point *corners);
+void gsh_perspective_correct_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src,
+                                   unsigned sw, unsigned sh, unsigned n,
+                                   const struct gs_point *corners);
+
 /* ---- synthetic frames + checksums on device (SURVEY.md 8c generator) ------------- */
 /* frame f = synth(w, h, seed0 + f): bit-identical to the CPU generator. */
 void gsh_synth_batch(uint8_t *dst, unsigned w, unsigned h, unsigned n, uint32_t seed0);
