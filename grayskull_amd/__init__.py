@@ -17,14 +17,14 @@ import os
 
 import numpy as np
 
-from ._abi import (BLOB_DTYPE, GsImage, GsLbpCascade, GsPoint, GsRect, KEYPOINT_DTYPE, MATCH_DTYPE, POINT_DTYPE,
+from ._abi import (BLOB_DTYPE, CONTOUR_DTYPE, GsImage, GsLbpCascade, GsPoint, GsRect, KEYPOINT_DTYPE, MATCH_DTYPE, POINT_DTYPE,
                    RECT_DTYPE)
 from .cascade import Cascade
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIBRARY = os.path.join(_HERE, "libgrayskull_hip.so")
 
-__all__ = ["Grayskull", "Cascade", "lib", "BLOB_DTYPE", "KEYPOINT_DTYPE", "MATCH_DTYPE", "POINT_DTYPE", "RECT_DTYPE"]
+__all__ = ["Grayskull", "Cascade", "lib", "BLOB_DTYPE", "CONTOUR_DTYPE", "KEYPOINT_DTYPE", "MATCH_DTYPE", "POINT_DTYPE", "RECT_DTYPE"]
 
 
 def _ptr(a):
@@ -85,6 +85,7 @@ _SIGS = {
     "gs_find_best_match": (GsPoint, [GsImage]),
     "gs_blobs": (C.c_uint, [GsImage, C.c_void_p, C.c_void_p, C.c_uint]),
     "gs_blob_corners": (None, [GsImage, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_trace_contour": (None, [GsImage, GsImage, C.c_void_p]),
     "gs_perspective_correct": (None, [GsImage, GsImage, C.c_void_p]),
     # runtime + batch (include/grayskull_hip.h)
     "gsh_version": (C.c_char_p, []),
@@ -151,6 +152,10 @@ _SIGS = {
                                        C.c_void_p]),
     "gsh_perspective_correct_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint,
                                               C.c_uint, C.c_void_p]),
+    "gsh_trace_contours_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint,
+                                         C.c_void_p, C.c_void_p]),
+    "gsh_blob_contour_starts_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint,
+                                              C.c_void_p, C.c_void_p]),
     "gsh_synth_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint32]),
     "gsh_checksum_batch": (None, [C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),
     # multi-GPU control plane of one-process host programs (csrc/gs_comm.cpp; RCCL looked up at run time)
@@ -347,6 +352,15 @@ class Grayskull:
         """grayskull.h:423: corners = 4 (x, y) pairs tl, tr, br, bl"""
         c = np.ascontiguousarray(np.asarray(corners, np.uint32).reshape(4, 2))
         self.c.gs_perspective_correct(_img(dst), _img(src), c.ctypes.data)
+
+    def trace_contour(self, img, visited, start):
+        """grayskull.h:446: the walk from start = (x, y) -> one CONTOUR_DTYPE record (box, start, length); `visited`
+        (h, w) uint8, host or device, is marked in place.  Where the reference's walk would never end, the values it
+        converges to."""
+        c = np.zeros(1, CONTOUR_DTYPE)
+        c["sx"], c["sy"] = int(start[0]) & 0xFFFFFFFF, int(start[1]) & 0xFFFFFFFF
+        self.c.gs_trace_contour(_img(img), _img(visited), c.ctypes.data)
+        return c[0]
 
     def integral(self, src, ii=None):  # grayskull.h:744
         if ii is None:
@@ -551,6 +565,21 @@ class Grayskull:
         n, sh, sw = self._nhw(src)
         _, dh, dw = self._nhw(dst)
         self.c.gsh_perspective_correct_batch(_ptr(dst), dw, dh, _ptr(src), sw, sh, n, _ptr(corners))
+
+    def trace_contours_batch(self, img, visited, contours, counts=None, status=None):
+        """gsh_trace_contours_batch: img, visited (n, h, w) uint8, contours (n, per_frame, 7) int32 (one 28-byte record
+        per row: see CONTOUR_DTYPE; `start` read, box and length written), counts (n) int32 or None, status
+        (n, per_frame) uint8 or None -- all device tensors; stream-ordered"""
+        n, h, w = self._nhw(img)
+        self.c.gsh_trace_contours_batch(_ptr(img), _ptr(visited), w, h, n, _ptr(contours), int(contours.shape[1]),
+                                        _ptr(counts), _ptr(status))
+
+    def blob_contour_starts_batch(self, labels, blobs, counts, contours):
+        """gsh_blob_contour_starts_batch: labels (n, h, w) uint16 [or int16], blobs (n, nblobs, 8) int32, counts (n) int32
+        or None as blobs_batch left them; contours (n, nblobs, 7) int32 receive each blob's raster-first pixel as start"""
+        n, h, w = self._nhw(labels)
+        self.c.gsh_blob_contour_starts_batch(_ptr(labels), w, h, n, _ptr(blobs), int(blobs.shape[1]), _ptr(counts),
+                                             _ptr(contours))
 
     def synth_batch(self, dst, seed0):
         n, h, w = self._nhw(dst)

@@ -9,6 +9,7 @@
  *   gs_comm.cpp     RCCL control plane for one-process multi-GPU host programs
  *   gs_fused.cpp, gs_box.cpp  kernels with their own compiler flags
  *   gs_blobs.cpp    connected components, blob corners, perspective correction (+ their C ABI)
+ *   gs_contour.cpp  contour tracing, contour starts of blob records (+ their C ABI)
  *
  * libgrayskull_hip.so: host runtime and C-ABI.
  *

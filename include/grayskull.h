@@ -19,9 +19,8 @@
  *     calling thread's stream (see grayskull_hip.h), synchronised before return
  *     unless gsh_set_async(1).
  *
- * Out of scope here: contours (gs_trace_contour, one sequential
- * walk per contour), PGM I/O, gs_alloc / gs_free.  Callers that need them
- * include the reference header for those functions.
+ * Out of scope here: PGM I/O, gs_alloc / gs_free.  Callers that
+ * need them include the reference header for those functions.
  */
 #ifndef GRAYSKULL_H
 #define GRAYSKULL_H
@@ -54,6 +53,11 @@ struct gs_blob {                                                   /* 32 B, ref 
   unsigned area;
   struct gs_rect box;
   struct gs_point centroid;
+};
+struct gs_contour {                                                /* 28 B, ref :36-40 */
+  struct gs_rect box;
+  struct gs_point start;
+  unsigned length;
 };
 struct gs_keypoint {                                               /* 48 B, ref :42-47 */
   struct gs_point pt;
@@ -187,6 +191,18 @@ GS_API void gs_blob_corners(struct gs_image img, gs_label *labels, struct gs_blo
                             struct gs_point c[4]);                              /* ref :404 */
 GS_API void gs_perspective_correct(struct gs_image dst, struct gs_image src,
                                    struct gs_point c[4]);                       /* ref :423, float32 bilinear */
+
+/* ---- contours (docs/design/contours.md) --------------------------------------------------------
+ * gs_trace_contour: the reference's walk from c->start (which need be neither inside the image nor foreground)
+ * over the 8-neighbours > 128 (not >= 128 as in gs_blobs), marking `visited` with 255 and counting in c->length
+ * the pixels it found unmarked; c->box by the reference's running expressions (box.w / box.h are NOT the extent of
+ * the bounding box when box.x / box.y dropped after they were set).  `c` is a host struct, so the call always
+ * synchronises; img.data and visited.data may each be a host or a device pointer and must not overlap.
+ * On many ordinary inputs -- features one pixel thick -- the reference's walk enters a cycle that never passes its
+ * stop test and the reference does NOT RETURN.  length, box and visited converge on such a walk; the library detects
+ * the cycle exactly and returns those limit values.  gsh_trace_contours_batch (grayskull_hip.h) also reports which
+ * walks were of that kind. */
+GS_API void gs_trace_contour(struct gs_image img, struct gs_image visited, struct gs_contour *c); /* ref :446 */
 
 /* 3x3 kernels for gs_filter, as the reference spells them (ref :249-253) */
 #define gs_sharpen ((struct gs_image){3, 3, (uint8_t[]){0, -1, 0, -1, 5, -1, 0, -1, 0}})

@@ -222,6 +222,24 @@ void gsh_perspective_correct_batch(uint8_t *dst, unsigned dw, unsigned dh, const
                                    unsigned sw, unsigned sh, unsigned n,
                                    const struct gs_point *corners);
 
+/* ---- contours (ref :446; docs/design/contours.md) -------------------------------------------------
+ * gsh_trace_contours_batch: frame f traces contours[f * per_frame + k] for k < counts[f] (counts == NULL: all
+ * per_frame; values above per_frame are clamped) ONE AFTER THE OTHER IN INDEX ORDER on frame f's own `visited` plane
+ * (n x w x h, the caller's bytes: 0 = not visited) -- what the same sequence of gs_trace_contour calls does: a
+ * later contour's length skips the pixels an earlier one marked.  Frames run side by side.  Of each record `start`
+ * is read, `box` and `length` are written.  status[f * per_frame + k] (may be NULL): 0 the walk ended, 1 it is
+ * endless in the reference (a state repeated; box, length and visited are the values it converges to), 2 the cap
+ * on the moves of one walk was reached (a bug).  img and visited must not overlap.
+ * gsh_blob_contour_starts_batch: for blob k < counts[f] of frame f (counts == NULL: all nblobs; labels, blobs,
+ * counts as gsh_blobs_batch left them), contours[f * nblobs + k].start = the raster-first pixel that carries the
+ * blob's label (it lies in row box.y, at x >= box.x); nothing else of the record is written. */
+void gsh_trace_contours_batch(const uint8_t *img, uint8_t *visited, unsigned w, unsigned h, unsigned n,
+                              struct gs_contour *contours, unsigned per_frame, const unsigned *counts,
+                              uint8_t *status);
+void gsh_blob_contour_starts_batch(const gs_label *labels, unsigned w, unsigned h, unsigned n,
+                                   const struct gs_blob *blobs, unsigned nblobs, const unsigned *counts,
+                                   struct gs_contour *contours);
+
 /* ---- synthetic frames + checksums on device (SURVEY.md 8c generator) ------------- */
 /* frame f = synth(w, h, seed0 + f): bit-identical to the CPU generator. */
 void gsh_synth_batch(uint8_t *dst, unsigned w, unsigned h, unsigned n, uint32_t seed0);
