@@ -43,8 +43,22 @@ void gsh_set_stream(void *s) {
     (void)hipStreamDestroy(c.stream);
     c.own_stream = false;
   }
+#ifndef GS_EMU
+  /* Scratch, caches and the side stream belong to the thread, not to the stream: whatever this thread enqueued on the
+   * caller's stream it leaves may still read or write them, so the stream it enters waits for that work on the device.
+   * (Leaving the library's own stream was a host sync above; a thread that never touched the device has enqueued nothing.) */
+  const hipStream_t old = c.stream;
+  const bool leaves_user = c.user_stream && c.device_set && old != (hipStream_t)s;
+  if (leaves_user) {
+    if (!c.ev_switch) GS_HIP(hipEventCreateWithFlags(&c.ev_switch, order_event_flags()));
+    GS_HIP(hipEventRecord(c.ev_switch, old));
+  }
+#endif
   c.stream = (hipStream_t)s;
   c.user_stream = s != nullptr;
+#ifndef GS_EMU
+  if (leaves_user) GS_HIP(hipStreamWaitEvent(c.s(), c.ev_switch, 0)); /* s == NULL: the own stream is created here */
+#endif
 }
 void *gsh_get_stream(void) { return (void *)ctx().s(); }
 void gsh_set_async(int on) { ctx().async = on != 0; }

@@ -189,6 +189,7 @@ struct Ctx {
   }
   hipStream_t side = nullptr; /* chunk overlap inside gsh_edge_pipeline_batch */
   hipEvent_t ev_join = nullptr, ev_chunk[kMaxChunks] = {};
+  hipEvent_t ev_switch = nullptr; /* gsh_set_stream: the stream entered waits for what was enqueued on the one left */
   void ensure_side() {
     if (side) return;
     {
@@ -273,6 +274,8 @@ struct Ctx {
       e = nullptr;
     }
     prof_n = 0;
+    if (ev_switch) (void)hipEventDestroy(ev_switch);
+    ev_switch = nullptr;
     if (side) {
       (void)hipStreamDestroy(side), (void)hipEventDestroy(ev_join);
       for (auto &e : ev_chunk) (void)hipEventDestroy(e), e = nullptr;

@@ -28,7 +28,16 @@ extern "C" {
 const char *gsh_version(void);
 int gsh_device_count(void);               /* 0 when no GPU is visible                 */
 void gsh_set_device(int ordinal);         /* per calling thread; default device 0      */
-void gsh_set_stream(void *hip_stream);    /* NULL => the library's own per-thread one   */
+/* gsh_set_stream selects the stream the calling thread's next calls are enqueued on (NULL => the library's own
+ * per-thread one).  The device scratch, the cascade / table caches and the internal side stream belong to the THREAD,
+ * not to the stream, so a switch orders the newly selected stream behind everything the thread has enqueued on the
+ * previous one: leaving the library's own stream synchronises the host with it and destroys it; leaving a caller's
+ * stream -- for another caller's stream or for NULL -- records an event on the stream left and makes the stream entered
+ * wait for it on the device (no host sync).  The caller guarantees that (a) the previous stream still exists when
+ * gsh_set_stream is called (destroy it after the switch, not before), (b) one thread's calls are issued from that
+ * thread only, and (c) work of its own that it enqueues on a stream it has switched away from is ordered against the
+ * library's later calls by its own means: the library orders only what went through it. */
+void gsh_set_stream(void *hip_stream);
 void *gsh_get_stream(void);
 void gsh_set_async(int on);               /* drop-in gs_* calls on device pointers skip
                                              the final stream sync when on             */

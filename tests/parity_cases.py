@@ -270,10 +270,9 @@ def _is_gpu(g):
     return "emulator" not in g.version()
 
 
-def match_random(g, o, n1, n2):
-    """gs_match_orb on random descriptors: partners at distance 0 / 3 / 40, some of them twice in the train set (ties: the first
-    index of the minimum wins, ref :690; equal best and second fail the 0.8 ratio test), three (max_matches, max_distance)"""
-    from grayskull_amd import KEYPOINT_DTYPE
+def random_descriptors(n1, n2):
+    """two keypoint sets with random descriptors: partners at distance 0 / 3 / 40, some of them twice in the train set (ties: the
+    first index of the minimum wins, ref :690; equal best and second fail the 0.8 ratio test)"""
     rng = np.random.RandomState(1000 * n1 + n2)
     k1, k2 = np.zeros(n1, KEYPOINT_DTYPE), np.zeros(n2, KEYPOINT_DTYPE)
     raw1, raw2 = k1.view(np.uint32).reshape(n1, 12), k2.view(np.uint32).reshape(n2, 12)
@@ -289,5 +288,11 @@ def match_random(g, o, n1, n2):
             raw2[j, 6] ^= 0xFFFF
         if i % 2 and n2 > 2:
             raw2[(j + n2 // 2) % n2, 4:] = raw2[j, 4:]
+    return k1, k2
+
+
+def match_random(g, o, n1, n2):
+    """gs_match_orb on random_descriptors(n1, n2), three (max_matches, max_distance)"""
+    k1, k2 = random_descriptors(n1, n2)
     for mm, md in ((n1 + 3, 60.0), (max(1, n1 // 2), 256.0), (n1, 2.0)):
         assert_same(g.match_orb(k1, k2, mm, md), o.match_orb(k1, k2, mm, md), "gs_match_orb %d x %d max=%d dist=%g" % (n1, n2, mm, md))
