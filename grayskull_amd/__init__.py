@@ -152,6 +152,10 @@ _SIGS = {
                                        C.c_void_p]),
     "gsh_perspective_correct_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint,
                                               C.c_uint, C.c_void_p]),
+    "gsh_blob_largest_batch": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]),
+    "gsh_blob_paint_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint,
+                                    C.c_void_p]),
+    "gsh_threshold_batch_dev_offset": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_int]),
     "gsh_trace_contours_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint,
                                          C.c_void_p, C.c_void_p]),
     "gsh_blob_contour_starts_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint,
@@ -565,6 +569,23 @@ class Grayskull:
         n, sh, sw = self._nhw(src)
         _, dh, dw = self._nhw(dst)
         self.c.gsh_perspective_correct_batch(_ptr(dst), dw, dh, _ptr(src), sw, sh, n, _ptr(corners))
+
+    def blob_largest_batch(self, blobs, counts, largest, index=None):
+        """gsh_blob_largest_batch: blobs (n, nblobs, 8) int32 and counts (n) int32 as blobs_batch left them; largest (n, 8)
+        int32 receives each frame's first record of maximum area, index (n) int32 or None its position (-1: no blob)"""
+        self.c.gsh_blob_largest_batch(_ptr(blobs), int(blobs.shape[1]), _ptr(counts), int(blobs.shape[0]), _ptr(largest),
+                                      _ptr(index))
+
+    def threshold_batch_dev_offset(self, img, thr, offset):
+        """gsh_threshold_batch_dev_offset: frame f in place at (uint8_t)(thr[f] + offset); thr (n) uint8"""
+        n, h, w = self._nhw(img)
+        self.c.gsh_threshold_batch_dev_offset(_ptr(img), w, h, n, _ptr(thr), int(offset))
+
+    def blob_paint_batch(self, dst, img, blobs, counts):
+        """gsh_blob_paint_batch: dst, img (n, h, w) uint8, blobs (n, nblobs, 8) int32, counts (n) int32 -- the picture
+        nanomagick's `blobs` verb draws, one per frame"""
+        n, h, w = self._nhw(img)
+        self.c.gsh_blob_paint_batch(_ptr(dst), _ptr(img), w, h, n, _ptr(blobs), int(blobs.shape[1]), _ptr(counts))
 
     def trace_contours_batch(self, img, visited, contours, counts=None, status=None):
         """gsh_trace_contours_batch: img, visited (n, h, w) uint8, contours (n, per_frame, 7) int32 (one 28-byte record

@@ -1,7 +1,9 @@
 /*
  * gs_blobs.cpp -- launchers and C ABI of connected components (gs_blobs, ref grayskull.h:330-402), blob corners
  * (gs_blob_corners, ref :404-421) and perspective correction (gs_perspective_correct, ref :423-444): the reference's
- * own names and signatures (include/grayskull.h) and the device-resident batch entry points (include/grayskull_hip.h).
+ * own names and signatures (include/grayskull.h) and the device-resident batch entry points (include/grayskull_hip.h),
+ * among them what nanomagick's `scan` and `blobs` verbs do with the records: each frame's largest blob and the picture of
+ * the padded boxes (ref nanomagick.c:160-169, :196-199).
  * The kernels and the definition of what they compute are in k_blobs.h.
  */
 #include "gs_internal.h"
@@ -76,6 +78,49 @@ static void launch_perspective(uint8_t *dst, unsigned dw, unsigned dh, const uin
     const unsigned nn = std::min(kMaxZ, n - f0);
     GS_LAUNCH(k_perspective, grid2d(dw, dh, nn), dim3(64, 4), 0, st, dst + (size_t)dw * dh * f0, dw, dh,
               src + (size_t)sw * sh * f0, sw, sh, corners + (size_t)8u * f0);
+  }
+}
+
+static void launch_largest(const BlobRec *blobs, unsigned nblobs, const unsigned *counts, unsigned n, BlobRec *largest,
+                           unsigned *index) {
+  hipStream_t st = ctx().s();
+  const dim3 block(nblobs <= 4096u ? 64u : 256u); /* one wave per frame; a block for long record lists */
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const unsigned nn = std::min(kMaxZ, n - f0);
+    GS_LAUNCH(k_blob_largest, dim3(nn), block, 0, st, blobs + (size_t)nblobs * f0, nblobs, counts + f0, largest + f0,
+              index ? index + f0 : nullptr);
+  }
+}
+
+/* rows per band of k_blob_paint: about 32 KB of pixels per block (eight 16-byte steps per lane), fewer while the launch
+ * has under four blocks per CU to hand out, never more than the coverage bits of a block hold; gsh_tune key 0 (rows per
+ * band) overrides the first two.  0: a row does not fit (w > kPaintBits - 15 = 65521) -- the two-pass fallback. */
+static unsigned paint_band_rows(unsigned w, unsigned h, unsigned n) {
+  if (w > kPaintBits - 15u) return 0;
+  const unsigned fit = (kPaintBits - 15u) / w;
+  unsigned R = (32768u + w - 1u) / w;
+  while (R > 1u && (size_t)n * ((h + R - 1u) / R) < (size_t)4u * topo().cus) R = (R + 1u) / 2u;
+  if (g_tune[0] > 0) R = (unsigned)g_tune[0];
+  return std::max(1u, std::min(std::min(R, fit), h));
+}
+
+static void launch_paint(uint8_t *dst, const uint8_t *img, unsigned w, unsigned h, unsigned n, const BlobRec *blobs, unsigned nblobs,
+                         const unsigned *counts) {
+  hipStream_t st = ctx().s();
+  const size_t np = (size_t)w * h;
+  const unsigned R = paint_band_rows(w, h, n);
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const unsigned nn = std::min(kMaxZ, n - f0);
+    uint8_t *d = dst + np * f0;
+    const uint8_t *s = img + np * f0;
+    const BlobRec *b = blobs + (size_t)nblobs * f0;
+    if (R) {
+      GS_LAUNCH(k_blob_paint, dim3((h + R - 1u) / R, nn), dim3(256), 0, st, d, s, w, h, R, b, nblobs, counts + f0);
+    } else {
+      const unsigned bx = (unsigned)std::max<size_t>(1, std::min<size_t>((np + 4095u) / 4096u, 2048));
+      GS_LAUNCH(k_blob_paint_base, dim3(bx, nn), dim3(256), 0, st, d, s, np);
+      GS_LAUNCH(k_blob_paint_fill, dim3(std::min(nblobs, 1024u), nn), dim3(256), 0, st, d, s, w, h, b, nblobs, counts + f0);
+    }
   }
 }
 
@@ -155,6 +200,22 @@ void gsh_perspective_correct_batch(uint8_t *dst, unsigned dw, unsigned dh, const
   GS_ASSERT(dst && src && corners && dw > 0 && dh > 0 && sw > 0 && sh > 0);
   if (n == 0) return;
   launch_perspective(dst, dw, dh, src, sw, sh, n, (const uint32_t *)corners);
+}
+
+void gsh_blob_largest_batch(const struct gs_blob *blobs, unsigned nblobs, const unsigned *counts, unsigned n,
+                            struct gs_blob *largest, unsigned *index) {
+  GS_ASSERT(blobs && counts && largest && nblobs > 0);
+  if (n == 0) return;
+  launch_largest((const BlobRec *)blobs, nblobs, counts, n, (BlobRec *)largest, index);
+}
+
+void gsh_blob_paint_batch(uint8_t *dst, const uint8_t *img, unsigned w, unsigned h, unsigned n, const struct gs_blob *blobs,
+                          unsigned nblobs, const unsigned *counts) {
+  GS_ASSERT(dst && img && blobs && counts && w > 0 && h > 0 && nblobs > 0);
+  GS_ASSERT((unsigned long long)w * h <= 0xffffffffull);
+  if (n == 0) return;
+  GS_ASSERT(dst + (size_t)w * h * n <= img || img + (size_t)w * h * n <= dst); /* dst is written while img is read */
+  launch_paint(dst, img, w, h, n, (const BlobRec *)blobs, nblobs, counts);
 }
 
 }  // extern "C"

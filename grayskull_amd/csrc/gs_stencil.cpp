@@ -398,7 +398,7 @@ void launch_histogram(const uint8_t *img, size_t frame_bytes, unsigned n, unsign
   }
 }
 void launch_threshold(uint8_t *img, size_t frame_bytes, unsigned n, const uint8_t *thr_dev,
-                      unsigned thr_const, hipStream_t on = nullptr) {
+                      unsigned thr_const, hipStream_t on = nullptr, int thr_off = 0) {
   if (n == 0) return;
   hipStream_t st = on ? on : ctx().s();
   const size_t chunks = frame_bytes / 16 + 2;
@@ -406,7 +406,7 @@ void launch_threshold(uint8_t *img, size_t frame_bytes, unsigned n, const uint8_
   for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
     const unsigned nn = std::min(kMaxZ, n - f0);
     GS_LAUNCH(k_threshold, dim3(bx, nn), dim3(256), 0, st, img + frame_bytes * f0, frame_bytes,
-              thr_dev ? thr_dev + f0 : nullptr, thr_const);
+              thr_dev ? thr_dev + f0 : nullptr, thr_const, thr_off);
   }
 }
 void launch_otsu(const uint8_t *img, unsigned w, unsigned h, unsigned n, unsigned *hist,
@@ -489,6 +489,12 @@ void gsh_threshold_batch(uint8_t *img, unsigned w, unsigned h, unsigned n, uint8
 void gsh_threshold_batch_dev(uint8_t *img, unsigned w, unsigned h, unsigned n, const uint8_t *thr) {
   GS_ASSERT(img && thr && w > 0 && h > 0);
   launch_threshold(img, (size_t)(w * h), n, thr, 0);
+}
+/* frame f at (uint8_t)(thr[f] + offset): gs_threshold(tmp, gs_otsu_threshold(tmp) + 10) of nanomagick's scan (ref
+ * nanomagick.c:191) with the thresholds still on the device; thr is not modified */
+void gsh_threshold_batch_dev_offset(uint8_t *img, unsigned w, unsigned h, unsigned n, const uint8_t *thr, int offset) {
+  GS_ASSERT(img && thr && w > 0 && h > 0);
+  launch_threshold(img, (size_t)(w * h), n, thr, 0, nullptr, offset);
 }
 /* gs_blur(radius) then gs_sobel into a zeroed image, per frame, in one pass (the fused kernel of
  * the pipeline without the Otsu / threshold half) */

@@ -26,7 +26,10 @@
  *                  same label reduce across the wave first)
  *   k_blob_compact per frame: the non-empty label slots in label order as struct gs_blob records, and their count
  *
- * Only atomicMin / atomicMax / atomicAdd are used.
+ * Only atomicMin / atomicMax / atomicAdd are used (k_blob_paint, further down: atomicOr on LDS words).
+ *
+ * Behind the three functions: k_blob_largest (each frame's first record of maximum area) and k_blob_paint (the picture
+ * nanomagick's `blobs` verb draws from the records), both described where they stand.
  */
 #ifndef GS_K_BLOBS_H
 #define GS_K_BLOBS_H
@@ -603,6 +606,216 @@ __global__ __launch_bounds__(256) void k_perspective(uint8_t *dst, unsigned dw, 
   const float p = ((float)c00 * (1 - dx) * (1 - dy)) + ((float)c01 * dx * (1 - dy)) + ((float)c10 * (1 - dx) * dy) +
                   ((float)c11 * dx * dy);
   dst[(size_t)blockIdx.z * dw * dh + (size_t)y * dw + x] = (uint8_t)(int)p; /* float -> uint8_t truncation (value < 256) */
+}
+
+/* ---- gsh_blob_largest_batch: the scan chain's "largest blob" (ref nanomagick.c:196-199) ---------------------------- */
+/* grid (frames), block 64 or 256: the FIRST record of maximum area among the first min(counts[f], nblobs) -- the
+ * reference's strict `>` -- as the maximum of the keys (area << 32) | ~index, like k_argmax_first (k_geom.h).  No record:
+ * largest[f] = 32 zero bytes, index[f] = 0xffffffff (the reference reads an uninitialised record there). */
+__global__ __launch_bounds__(256) void k_blob_largest(const BlobRec *blobs, unsigned nblobs, const unsigned *counts,
+                                                      BlobRec *largest, unsigned *index) {
+  __shared__ unsigned long long part[4];
+  const unsigned tid = threadIdx.x, nw = blockDim.x >> 6;
+  const BlobRec *bf = blobs + (size_t)blockIdx.x * nblobs;
+  const unsigned c = counts[blockIdx.x], cnt = c < nblobs ? c : nblobs;
+  unsigned long long best = 0; /* below every key: ~i = 0 needs i = 0xffffffff >= cnt */
+  for (unsigned i = tid; i < cnt; i += blockDim.x) {
+    const unsigned long long key = ((unsigned long long)bf[i].area << 32) | (0xffffffffu - i);
+    best = key > best ? key : best;
+  }
+  best = wave_max_u64(best);
+  if ((tid & 63u) == 0) part[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+    for (unsigned q = 1; q < nw; q++) best = part[q] > best ? part[q] : best;
+    part[0] = best;
+  }
+  __syncthreads();
+  const unsigned at = 0xffffffffu - (unsigned)part[0]; /* cnt == 0: part[0] == 0, at == 0xffffffff */
+  if (tid < 8u) ((uint32_t *)(largest + blockIdx.x))[tid] = cnt ? ((const uint32_t *)(bf + at))[tid] : 0u;
+  if (tid == 0 && index) index[blockIdx.x] = at;
+}
+
+/* ---- gsh_blob_paint_batch: the picture nanomagick's `blobs` verb draws (ref nanomagick.c:160-169) ------------------
+ * dst = 0; every record's padded box := 128; every pixel with img > 128 := 255.  The reference's loops are INCLUSIVE
+ * (y1 <= y <= y2, x1 <= x <= x2, x2 <= w, y2 <= h) and write the linear index y * w + x, so a box that reaches the right
+ * edge also paints column 0 of the next row, and one that reaches the bottom addresses indices >= w * h: the reference
+ * writes past its buffer there, the library drops them.  So a box is a set of SPANS of the frame's linear index, one per
+ * row y: [y w + x1, y w + x2] cut at w h, and the kernel works on the linear index throughout.
+ *
+ * One pass, 2 B/px: a block owns a band of R rows of one frame (linear range [r0 w, r1 w)).  It builds the band's coverage
+ * as one BIT per pixel in LDS -- the spans of the records that reach the band are OR-ed in word-wise -- and then streams
+ * the band: 16 bytes of img in, 16 bytes of dst out per lane-step (dst chunks 16-byte aligned, bit 0 of the coverage is the
+ * byte at dst's band address rounded down to 16, so a chunk's 16 bits are one half of one LDS word; the ragged ends of
+ * the band go bytewise).
+ *
+ * Records: lanes read 256 records per step.  Records are in label order = raster order of each blob's first pixel, which
+ * lies in row box.y: box.y never decreases, so a wave stops after the step in which it saw a padded box that starts
+ * at or below the band's end.  A lane ORs a small box itself; a box of more than kPaintOwn (row, word) pairs in the band
+ * is handed to its wave, whose 64 lanes share the pairs (a frame-filling box: ~2000 ORs per band, 33 per lane), and the
+ * bands of a frame are independent blocks -- nothing serialises on one wave. */
+constexpr unsigned kPaintWords = 2048;            /* coverage words per block: 8 KB of LDS, 8 blocks of 256 per CU */
+constexpr unsigned kPaintBits = kPaintWords * 32; /* a band has at most kPaintBits - 15 pixels (15: the alignment phase) */
+constexpr unsigned kPaintOwn = 8;                 /* (row, word) pairs a lane ORs alone */
+
+/* per byte: x > 128 ? 0xff : 0 (bit 7 set and a low bit set) */
+GS_DEV uint32_t gt128_bytes(uint32_t x) { return ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) & x & 0x80808080u) >> 7) * 0xffu; }
+/* 4 coverage bits -> 128 in the covered bytes (bit i -> byte i) */
+GS_DEV uint32_t cov_bytes4(uint32_t b) { return (((b & 0xfu) * 0x00204081u) & 0x01010101u) << 7; }
+
+/* the reference's bounds in its own mixed arithmetic (nanomagick.c:162-164): x1, y1 through int, x2, y2 in wrapping u32 */
+struct PaintBox {
+  unsigned x1, y1, x2, y2;
+};
+GS_DEV PaintBox paint_box(const BlobRec &b, unsigned w, unsigned h) {
+  const int ix = (int)(b.bx - 2u), iy = (int)(b.by - 2u);
+  const unsigned ex = b.bx + b.bw + 2u, ey = b.by + b.bh + 2u;
+  return PaintBox{ix > 0 ? (unsigned)ix : 0u, iy > 0 ? (unsigned)iy : 0u, ex < w ? ex : w, ey < h ? ey : h};
+}
+/* row y of a box as coverage bits of the band [lo, hi) (bit = linear index - lo + ph): false when it misses the band */
+GS_DEV bool paint_row_bits(unsigned y, unsigned x1, unsigned x2, unsigned w, size_t lo, size_t hi, unsigned ph, unsigned &a,
+                           unsigned &b) {
+  size_t s = (size_t)y * w + x1, e = (size_t)y * w + x2;
+  s = s < lo ? lo : s;
+  if (e >= hi) e = hi - 1; /* hi > lo >= 0 */
+  if (s > e || e < lo) return false;
+  a = (unsigned)(s - lo) + ph, b = (unsigned)(e - lo) + ph;
+  return true;
+}
+
+/* grid (ceil(h / R), frames), block 256; R * w + 15 <= kPaintBits */
+__global__ __launch_bounds__(256) void k_blob_paint(uint8_t *dst, const uint8_t *img, unsigned w, unsigned h, unsigned R,
+                                                    const BlobRec *blobs, unsigned nblobs, const unsigned *counts) {
+  __shared__ uint32_t cov[kPaintWords];
+  const unsigned tid = threadIdx.x, lane = tid & 63u;
+  const unsigned r0 = blockIdx.x * R, r1 = r0 + R < h ? r0 + R : h;
+  const size_t np = (size_t)w * h, lo = (size_t)r0 * w, hi = (size_t)r1 * w;
+  if (r0 >= h) return; /* whole block */
+  uint8_t *d = dst + (size_t)blockIdx.y * np + lo;
+  const uint8_t *s = img + (size_t)blockIdx.y * np + lo;
+  const uintptr_t a0 = (uintptr_t)d & ~(uintptr_t)15;
+  const unsigned ph = (unsigned)((uintptr_t)d - a0);
+  const size_t nbits = (size_t)ph + (hi - lo);
+  if (nbits > kPaintBits) return; /* the launcher never asks for it */
+  const unsigned nwords = (unsigned)((nbits + 31u) / 32u);
+  for (unsigned k = tid; k < nwords; k += 256u) cov[k] = 0u;
+  __syncthreads();
+
+  const BlobRec *bf = blobs + (size_t)blockIdx.y * nblobs;
+  const unsigned c = counts[blockIdx.y], cnt = c < nblobs ? c : nblobs;
+  for (unsigned base = 0; base < cnt; base += 256u) { /* block-uniform bound, wave-uniform exit */
+    const unsigned i = base + tid;
+    bool below = false, hit = false;
+    unsigned x1 = 0, x2 = 0, ya = 0, yb = 0;
+    if (i < cnt) {
+      const PaintBox p = paint_box(bf[i], w, h);
+      below = p.y1 >= r1;
+      if (!below && p.x1 <= p.x2 && p.y1 <= p.y2) {
+        /* the rows whose spans reach the band: its own, and the one above when the span wraps to column 0 (x2 == w) */
+        const unsigned first = (r0 > 0 && p.x2 == w) ? r0 - 1u : r0;
+        ya = p.y1 > first ? p.y1 : first, yb = p.y2 < r1 - 1u ? p.y2 : r1 - 1u;
+        hit = ya <= yb;
+        x1 = p.x1, x2 = p.x2;
+      }
+    }
+    const unsigned wpr = (x2 - x1) / 32u + 2u; /* words a row's span can touch */
+    const bool own = hit && (yb - ya + 1u) * wpr <= kPaintOwn;
+    if (own) {
+      for (unsigned y = ya; y <= yb; y++) {
+        unsigned a, b;
+        if (!paint_row_bits(y, x1, x2, w, lo, hi, ph, a, b)) continue;
+        const uint32_t ma = ~0u << (a & 31u), mb = ~0u >> (31u - (b & 31u));
+        const unsigned wa = a >> 5, wb = b >> 5;
+        if (wa == wb) {
+          atomicOr(&cov[wa], ma & mb);
+        } else {
+          atomicOr(&cov[wa], ma);
+          for (unsigned k = wa + 1u; k < wb; k++) atomicOr(&cov[k], ~0u);
+          atomicOr(&cov[wb], mb);
+        }
+      }
+    }
+    uint64_t big = ballot(hit && !own);
+    while (big) { /* wave-uniform: the wave's lanes share one large box's (row, word) pairs */
+      const unsigned src = (unsigned)__builtin_ctzll(big);
+      big &= big - 1ull;
+      const unsigned X1 = readlane_at(x1, src), X2 = readlane_at(x2, src), YA = readlane_at(ya, src), YB = readlane_at(yb, src);
+      const unsigned per = (X2 - X1) / 32u + 2u, total = (YB - YA + 1u) * per;
+      for (unsigned t = lane; t < total; t += 64u) {
+        const unsigned row = t / per, k = t - row * per;
+        unsigned a, b;
+        if (!paint_row_bits(YA + row, X1, X2, w, lo, hi, ph, a, b)) continue;
+        const unsigned wa = a >> 5, wb = b >> 5, word = wa + k;
+        if (word > wb) continue;
+        uint32_t m = ~0u;
+        if (word == wa) m &= ~0u << (a & 31u);
+        if (word == wb) m &= ~0u >> (31u - (b & 31u));
+        atomicOr(&cov[word], m);
+      }
+    }
+    if (ballot(below)) break;
+  }
+  __syncthreads();
+
+  /* stream the band: chunk ci = bytes [16 ci, 16 ci + 16) from a0 = coverage bits 16 ci .. 16 ci + 15 */
+  const size_t nch = (nbits + 15u) / 16u;
+  const bool same_phase = ((((uintptr_t)s) ^ ((uintptr_t)d)) & 15u) == 0u;
+  for (size_t ci = tid; ci < nch; ci += 256u) {
+    const size_t b0 = ci * 16u;
+    const uint32_t bits = (cov[ci >> 1] >> (16u * (unsigned)(ci & 1u))) & 0xffffu;
+    if (b0 >= ph && b0 + 16u <= nbits) {
+      uint8_t *p = (uint8_t *)(a0 + b0);
+      const uint8_t *q = s + (b0 - ph);
+      U4 v;
+#ifndef GS_EMU
+      typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+      if (same_phase) { /* read once, written once: stream both (k_threshold) */
+        const v4u t = __builtin_nontemporal_load((const v4u *)q);
+        v = U4{t.x, t.y, t.z, t.w};
+      } else {
+        v = load_u32x4_any(q);
+      }
+#else
+      (void)same_phase;
+      v = load_u32x4_any(q);
+#endif
+      v.x = gt128_bytes(v.x) | cov_bytes4(bits), v.y = gt128_bytes(v.y) | cov_bytes4(bits >> 4);
+      v.z = gt128_bytes(v.z) | cov_bytes4(bits >> 8), v.w = gt128_bytes(v.w) | cov_bytes4(bits >> 12);
+#ifndef GS_EMU
+      __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, (v4u *)p);
+#else
+      store_u32x4(p, v);
+#endif
+    } else { /* the band's ragged first / last chunk */
+      const size_t k0 = b0 < ph ? ph : b0, k1 = b0 + 16u > nbits ? nbits : b0 + 16u;
+      for (size_t k = k0; k < k1; k++) d[k - ph] = s[k - ph] > 128 ? 255 : ((bits >> (unsigned)(k - b0)) & 1u) ? 128 : 0;
+    }
+  }
+}
+
+/* Frames wider than kPaintBits - 15 pixels (not one row's bits fit the block's LDS): dst = img > 128 ? 255 : 0, then the
+ * boxes' pixels that are not 255 := 128, two plain passes.  grid (blocks, frames), block 256. */
+__global__ __launch_bounds__(256) void k_blob_paint_base(uint8_t *dst, const uint8_t *img, size_t np) {
+  uint8_t *d = dst + (size_t)blockIdx.y * np;
+  const uint8_t *s = img + (size_t)blockIdx.y * np;
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < np; i += (size_t)gridDim.x * 256u) d[i] = s[i] > 128 ? 255 : 0;
+}
+__global__ __launch_bounds__(256) void k_blob_paint_fill(uint8_t *dst, const uint8_t *img, unsigned w, unsigned h,
+                                                         const BlobRec *blobs, unsigned nblobs, const unsigned *counts) {
+  const size_t np = (size_t)w * h;
+  uint8_t *d = dst + (size_t)blockIdx.y * np;
+  const uint8_t *s = img + (size_t)blockIdx.y * np;
+  const BlobRec *bf = blobs + (size_t)blockIdx.y * nblobs;
+  const unsigned c = counts[blockIdx.y], cnt = c < nblobs ? c : nblobs;
+  for (unsigned i = blockIdx.x; i < cnt; i += gridDim.x) {
+    const PaintBox p = paint_box(bf[i], w, h);
+    if (p.x1 > p.x2 || p.y1 > p.y2) continue;
+    const size_t bw = (size_t)(p.x2 - p.x1) + 1u, total = bw * ((size_t)(p.y2 - p.y1) + 1u);
+    for (size_t t = threadIdx.x; t < total; t += 256u) {
+      const size_t row = t / bw, at = ((size_t)p.y1 + row) * w + p.x1 + (t - row * bw);
+      if (at < np && !(s[at] > 128)) d[at] = 128;
+    }
+  }
 }
 
 }  // namespace gs

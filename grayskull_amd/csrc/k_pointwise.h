@@ -34,11 +34,12 @@ GS_DEV uint32_t swar_gt_u8(uint32_t x, uint32_t trep) {
   return (gt >> 7) * 0xffu;
 }
 
-/* ref :225-228, in place.  grid (blocks, n frames); thr_dev (per-frame) overrides thr_const */
+/* ref :225-228, in place.  grid (blocks, n frames); thr_dev (per-frame) overrides thr_const; thr_off is added to a
+ * per-frame threshold and the sum converted the way C passes an int to a uint8_t parameter (250 + 10 -> 4) */
 __global__ __launch_bounds__(256) void k_threshold(uint8_t *img, size_t frame_bytes,
-                                                   const uint8_t *thr_dev, unsigned thr_const) {
+                                                   const uint8_t *thr_dev, unsigned thr_const, int thr_off = 0) {
   uint8_t *base = img + (size_t)blockIdx.y * frame_bytes;
-  const unsigned t = thr_dev ? thr_dev[blockIdx.y] : thr_const;
+  const unsigned t = thr_dev ? ((unsigned)((int)thr_dev[blockIdx.y] + thr_off) & 0xffu) : thr_const;
   const uint32_t trep = t * 0x01010101u;
   const Chunking c = make_chunking(base, frame_bytes);
   for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < c.nchunks;

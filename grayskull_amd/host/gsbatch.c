@@ -17,7 +17,12 @@
  *
  * Verbs (nanomagick.c:52-141, same argument meaning / error text):
  *   resize <w> <h> | crop <x> <y> <w> <h> | blur <r> | threshold <t|otsu> | adaptive <r> <c> |
- *   sobel | morph <erode|dilate> <n>
+ *   sobel | morph <erode|dilate> <n> | blobs <n> | scan
+ *   blobs <n>           gs_blobs (cap n) and nanomagick's picture of it (nanomagick.c:143-170): the boxes padded by 2 in
+ *                       grey, the pixels above 128 in white -- gsh_blobs_batch + gsh_blob_paint_batch over the slice
+ *   scan                the document scanner (nanomagick.c:186-210): blur 1, Otsu + 10, gs_blobs (1000), the largest
+ *                       blob's corners, the INPUT frame warped into 800 x 1000; device-resident over the slice, one
+ *                       download of the counts (a frame without a blob fails: "Error: no blob found")
  * and, as the LAST stage of a chain, the two feature verbs (nanomagick.c:217-243, :347-376):
  *   keypoints <n> <t>   gs_fast (cap 5000, threshold t) on the GPU; the n strongest are drawn as
  *                       crosses like nanomagick does and listed in <out>.keypoints.txt ("x y response")
@@ -52,13 +57,23 @@
 
 #include "grayskull_hip.h"
 
+/* The connected-components unit of the library (csrc/gs_blobs.cpp) is bound weakly: the driver still links against a
+ * build of the library that leaves that unit out (the sanitizer build of tests/test_gsbatch.py is one); `blobs` and
+ * `scan` then end with a message instead of the link failing for every verb. */
+#pragma weak gsh_blobs_batch
+#pragma weak gsh_blob_paint_batch
+#pragma weak gsh_blob_largest_batch
+#pragma weak gsh_blob_corners_batch
+#pragma weak gsh_perspective_correct_batch
+
 static size_t kSliceBytes = (size_t)64 << 20; /* per plane and slice (8 4K frames); GSBATCH_SLICE_BYTES overrides.
    Measured on 64 4K files (profiles/r01i_gsbatch_64x4k.log): page-locking the staging buffer costs ~85 ms
    per GiB, so small slices win: 0.44 s wall at 64 MiB vs 0.64 s at 1 GiB */
 
-enum verb { V_RESIZE, V_CROP, V_BLUR, V_THRESHOLD, V_ADAPTIVE, V_SOBEL, V_MORPH, V_KEYPOINTS, V_FACES, V_ORB };
+enum verb { V_RESIZE, V_CROP, V_BLUR, V_THRESHOLD, V_ADAPTIVE, V_SOBEL, V_MORPH, V_BLOBS, V_SCAN, V_KEYPOINTS, V_FACES, V_ORB };
 #define IS_TERMINAL(v) ((v) == V_KEYPOINTS || (v) == V_FACES || (v) == V_ORB)
 enum { kFastCap = 5000, kFaceCap = 100, kOrbKps = 2500, kOrbMatches = 300 }; /* nanomagick.c:224, :349, :301-306 */
+enum { kScanBlobs = 1000, kScanW = 800, kScanH = 1000, kBlobCapMax = 65535 }; /* nanomagick.c:194, :204; gs_label is u16 */
 
 struct stage {
   enum verb v;
@@ -74,6 +89,7 @@ static const struct {
   int argc;
 } verbs[] = {{"resize", V_RESIZE, 2},     {"crop", V_CROP, 4},   {"blur", V_BLUR, 1}, {"threshold", V_THRESHOLD, 1},
              {"adaptive", V_ADAPTIVE, 2}, {"sobel", V_SOBEL, 0}, {"morph", V_MORPH, 2},
+             {"blobs", V_BLOBS, 1},       {"scan", V_SCAN, 0},
              {"keypoints", V_KEYPOINTS, 2}, {"faces", V_FACES, 1}, {"orb", V_ORB, 1}, {NULL, V_SOBEL, 0}};
 
 struct frame {
@@ -94,7 +110,7 @@ static void usage(const char *app) {
   fprintf(stderr,
           "Usage: %s [-v] [--gpus N] [--cascade blob] -o <outdir> <verb> [params] [: <verb> [params]]... -- in1.pgm [in2.pgm ...]\n"
           "Verbs: resize <w> <h> | crop <x> <y> <w> <h> | blur <r> | threshold <t|otsu> |\n"
-          "       adaptive <r> <c> | sobel | morph <erode|dilate> <n>\n"
+          "       adaptive <r> <c> | sobel | morph <erode|dilate> <n> | blobs <n> | scan\n"
           "       last stage only: keypoints <n> <t> | faces <n> (needs --cascade) | orb <template.pgm>\n",
           app);
 }
@@ -196,6 +212,13 @@ static int parse_stages(int argc, char **argv, int *pos, struct stage *st, int m
     n++;
   }
   *pos = i;
+  for (i = 0; i < n; i++)
+    if ((st[i].v == V_BLOBS || st[i].v == V_SCAN) && !(gsh_blobs_batch && gsh_blob_paint_batch && gsh_blob_largest_batch &&
+                                                       gsh_blob_corners_batch && gsh_perspective_correct_batch)) {
+      fprintf(stderr, "Error: this libgrayskull_hip was built without connected components: no '%s'\n",
+              st[i].v == V_BLOBS ? "blobs" : "scan");
+      return -1;
+    }
   for (i = 0; i + 1 < n; i++)
     if (IS_TERMINAL(st[i].v)) {
       fprintf(stderr, "Error: '%s' writes detections, not an image to filter on: it must be the last stage\n",
@@ -236,6 +259,10 @@ static int check_stage(const struct stage *s, unsigned w, unsigned h) {
     case V_FACES: /* nanomagick.c:351-355 */
       if (s->a[0] <= 0) return fprintf(stderr, "Error: minimum neighbors must be positive\n"), -1;
       break;
+    case V_BLOBS: /* nanomagick.c:144-148 */
+      if (s->a[0] <= 0) return fprintf(stderr, "Error: Invalid number of blobs\n"), -1;
+      break;
+    case V_SCAN:
     case V_ORB:
     case V_SOBEL: break;
   }
@@ -245,6 +272,18 @@ static int check_stage(const struct stage *s, unsigned w, unsigned h) {
 static void stage_out_size(const struct stage *s, unsigned *w, unsigned *h) {
   if (s->v == V_RESIZE) *w = (unsigned)s->a[0], *h = (unsigned)s->a[1];
   if (s->v == V_CROP) *w = (unsigned)s->a[2], *h = (unsigned)s->a[3];
+  if (s->v == V_SCAN) *w = kScanW, *h = kScanH; /* nanomagick.c:204 */
+}
+
+/* records per frame a `blobs` / `scan` stage asks gs_blobs for on w x h frames.  A frame has at most (w h + 1) / 2 start
+ * pixels, and from 65535 on every nblobs behaves alike (the u16 label counter: docs/design/blobs.md): below both bounds
+ * the result is the one of the number typed, and the record buffers stay small. */
+static unsigned stage_nblobs(const struct stage *s, unsigned w, unsigned h) {
+  const unsigned long long most = ((unsigned long long)w * h + 1) / 2;
+  unsigned long long nb = s->v == V_SCAN ? (unsigned long long)kScanBlobs : (unsigned long long)s->a[0];
+  if (s->v != V_BLOBS && s->v != V_SCAN) return 0;
+  if (s->v == V_BLOBS && nb > most) nb = most;
+  return (unsigned)(nb > kBlobCapMax ? kBlobCapMax : nb);
 }
 
 struct planes {
@@ -252,6 +291,12 @@ struct planes {
   unsigned *hist;       /* n * 256 u32 */
   uint8_t *thr_dev;     /* n */
   uint8_t *thr_host;    /* n */
+  /* `blobs` / `scan` scratch, per group like the terminal verbs' buffers (NULL without such a stage) */
+  gs_label *labels;         /* n * largest frame such a stage reads */
+  struct gs_blob *recs;     /* n * most records such a stage asks for */
+  struct gs_blob *one;      /* n: each frame's largest blob */
+  struct gs_point *corners; /* n * 4 */
+  unsigned *cnt_dev, *cnt_host; /* n */
 };
 
 static void swap_planes(struct planes *p) {
@@ -342,6 +387,32 @@ static void run_stages(const struct stage *st, int ns, struct planes *p, unsigne
         }
         w = ow;
         h = oh;
+        swap_planes(p);
+        break;
+      }
+      case V_BLOBS: { /* nanomagick.c:149-169: the output image comes from calloc, the paint kernel writes every byte */
+        const unsigned nb = stage_nblobs(s, w, h);
+        gsh_blobs_batch(p->cur, w, h, n, p->labels, p->recs, p->cnt_dev, nb);
+        gsh_blob_paint_batch(p->other, p->cur, w, h, n, p->recs, nb, p->cnt_dev);
+        swap_planes(p);
+        break;
+      }
+      case V_SCAN: { /* nanomagick.c:186-210 over the whole slice; `other` is its tmp, then the output */
+        gsh_blur_batch(p->other, p->cur, w, h, n, 1);
+        gsh_otsu_batch(p->other, w, h, n, p->hist, p->thr_dev);
+        gsh_threshold_batch_dev_offset(p->other, w, h, n, p->thr_dev, 10);
+        gsh_blobs_batch(p->other, w, h, n, p->labels, p->recs, p->cnt_dev, kScanBlobs);
+        gsh_blob_largest_batch(p->recs, kScanBlobs, p->cnt_dev, n, p->one, NULL);
+        gsh_blob_corners_batch(p->other, p->labels, w, h, n, p->one, p->corners);
+        gsh_perspective_correct_batch(p->other, kScanW, kScanH, p->cur, w, h, n, p->corners);
+        /* the reference reads an uninitialised record when gs_blobs finds nothing: such a frame fails here */
+        gsh_download(p->cnt_host, p->cnt_dev, (size_t)n * sizeof(unsigned));
+        for (f = 0; f < n; f++)
+          if (p->cnt_host[f] == 0 && !failed[f]) {
+            fprintf(stderr, "Error: no blob found\n");
+            failed[f] = 1;
+          }
+        w = kScanW, h = kScanH;
         swap_planes(p);
         break;
       }
@@ -545,7 +616,8 @@ static void *worker(void *arg) {
 
   for (g = 0; g < jb->ngroups; g++) {
     unsigned w = 0, h = 0, ngroup = 0, n, lo, hi, f, ow, oh;
-    size_t max_fb, fb;
+    size_t max_fb, fb, lab_px = 0;
+    unsigned rec_max = 0;
     struct planes p;
     int *failed, bad = 0;
     uint8_t *stage;
@@ -571,6 +643,11 @@ static void *worker(void *arg) {
     ow = w, oh = h, max_fb = (size_t)w * h;
     for (i = 0; i < ns && !bad; i++) {
       if (check_stage(&st[i], ow, oh) != 0) bad = 1;
+      if (!bad && stage_nblobs(&st[i], ow, oh)) { /* what the stage's labels and records need, at the size it runs at */
+        const unsigned nb = st[i].v == V_SCAN ? (unsigned)kScanBlobs : stage_nblobs(&st[i], ow, oh);
+        if ((size_t)ow * oh > lab_px) lab_px = (size_t)ow * oh;
+        if (nb > rec_max) rec_max = nb;
+      }
       stage_out_size(&st[i], &ow, &oh);
       if ((size_t)ow * oh > max_fb) max_fb = (size_t)ow * oh;
     }
@@ -592,6 +669,11 @@ static void *worker(void *arg) {
      * staging buffer and the two device planes stay bounded whatever the number of files */
     cap = (unsigned)(kSliceBytes / max_fb);
     if (term && cap > 256) cap = 256; /* 240 KB of keypoint records / 4 bytes of integral per pixel per frame */
+    if (rec_max) { /* blobs / scan: 2 bytes of label per pixel and rec_max 32-byte records per frame */
+      const size_t by_recs = kSliceBytes / ((size_t)rec_max * sizeof(struct gs_blob));
+      if (cap > 256) cap = 256;
+      if (by_recs < cap) cap = (unsigned)by_recs;
+    }
     cap = cap < 1 ? 1 : cap > n ? n : cap;
     t0 = now_ms();
     p.cur = (uint8_t *)gsh_malloc(max_fb * cap);
@@ -599,6 +681,16 @@ static void *worker(void *arg) {
     p.hist = (unsigned *)gsh_malloc((size_t)cap * 256 * sizeof(unsigned));
     p.thr_dev = (uint8_t *)gsh_malloc(cap);
     p.thr_host = (uint8_t *)malloc(cap);
+    p.labels = NULL, p.recs = NULL, p.one = NULL, p.corners = NULL, p.cnt_dev = NULL, p.cnt_host = NULL;
+    if (rec_max) {
+      p.labels = (gs_label *)gsh_malloc(lab_px * cap * sizeof(gs_label));
+      p.recs = (struct gs_blob *)gsh_malloc((size_t)cap * rec_max * sizeof(struct gs_blob));
+      p.one = (struct gs_blob *)gsh_malloc((size_t)cap * sizeof(struct gs_blob));
+      p.corners = (struct gs_point *)gsh_malloc((size_t)cap * 4 * sizeof(struct gs_point));
+      p.cnt_dev = (unsigned *)gsh_malloc((size_t)cap * sizeof(unsigned));
+      p.cnt_host = (unsigned *)malloc((size_t)cap * sizeof(unsigned));
+      if (!p.cnt_host) gsb_oom(__LINE__);
+    }
     failed = (int *)malloc(cap * sizeof *failed);
     stage = (uint8_t *)gsh_host_alloc(max_fb * cap); /* page-locked: one DMA each way per slice */
     sums_dev = (uint64_t *)gsh_malloc((size_t)cap * 8);
@@ -785,6 +877,12 @@ static void *worker(void *arg) {
     gsh_free(p.other);
     gsh_free(p.hist);
     gsh_free(p.thr_dev);
+    gsh_free(p.labels);
+    gsh_free(p.recs);
+    gsh_free(p.one);
+    gsh_free(p.corners);
+    gsh_free(p.cnt_dev);
+    free(p.cnt_host);
     gsh_host_free(stage);
     gsh_free(orb_buf);
     gsh_free(score);

@@ -125,6 +125,10 @@ void gsh_otsu_batch(const uint8_t *img, unsigned w, unsigned h, unsigned n, unsi
                     uint8_t *thr);
 void gsh_threshold_batch(uint8_t *img, unsigned w, unsigned h, unsigned n, uint8_t thresh);
 void gsh_threshold_batch_dev(uint8_t *img, unsigned w, unsigned h, unsigned n, const uint8_t *thr);
+/* frame f thresholded at (uint8_t)(thr[f] + offset) -- the conversion C performs for gs_threshold(img,
+ * gs_otsu_threshold(img) + 10) (ref nanomagick.c:191): Otsu 250 + 10 thresholds at 4.  thr is not modified. */
+void gsh_threshold_batch_dev_offset(uint8_t *img, unsigned w, unsigned h, unsigned n, const uint8_t *thr,
+                                    int offset);
 
 /* gs_blur(src, radius) followed by gs_sobel into a zeroed dst, per frame, in one pass over the frame
  * for radius 1..3 (the blurred image stays in registers; ref :268, :306) */
@@ -230,6 +234,20 @@ void gsh_blob_corners_batch(const uint8_t *img, const gs_label *labels, unsigned
 void gsh_perspective_correct_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src,
                                    unsigned sw, unsigned sh, unsigned n,
                                    const struct gs_point *corners);
+/* gsh_blob_largest_batch: largest[f] = the FIRST record of maximum area among the first min(counts[f], nblobs) of
+ * frame f (the strict `>` of ref nanomagick.c:197-199), index[f] (index may be NULL) its position; a frame without
+ * blobs gets 32 zero bytes and index 0xffffffff (the reference reads an uninitialised record there).
+ * gsh_blob_paint_batch: the picture nanomagick's `blobs` verb draws (ref nanomagick.c:160-169) from blobs / counts as
+ * gsh_blobs_batch left them (records in label order: box.y never decreases): dst (n x w x h, every byte written, must
+ * not overlap img) = 255 where img > 128, else 128 inside a blob's box padded by 2, else 0.  The reference's loops are
+ * inclusive and address y * w + x with x <= w, y <= h: a box that reaches the right edge also marks column 0 of the
+ * next row, and where the reference would write at or past w * h (outside its buffer) nothing is written.  One pass
+ * over the pixels; frames wider than 65521 pixels take two.  GSH_TUNE_STRIP_BAND_ROWS also sets this kernel's rows
+ * per band.  Both are stream-ordered, all pointers device pointers. */
+void gsh_blob_largest_batch(const struct gs_blob *blobs, unsigned nblobs, const unsigned *counts, unsigned n,
+                            struct gs_blob *largest, unsigned *index);
+void gsh_blob_paint_batch(uint8_t *dst, const uint8_t *img, unsigned w, unsigned h, unsigned n,
+                          const struct gs_blob *blobs, unsigned nblobs, const unsigned *counts);
 
 /* ---- contours (ref :446; docs/design/contours.md) -------------------------------------------------
  * gsh_trace_contours_batch: frame f traces contours[f * per_frame + k] for k < counts[f] (counts == NULL: all
