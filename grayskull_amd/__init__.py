@@ -112,6 +112,7 @@ _SIGS = {
     "gsh_sobel_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
     "gsh_erode_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
     "gsh_dilate_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_morph_batch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_uint]),
     "gsh_histogram_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]),
     "gsh_otsu_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
     "gsh_threshold_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint8]),
@@ -450,6 +451,12 @@ class Grayskull:
     def dilate_batch(self, dst, src):
         n, h, w = self._nhw(src)
         self.c.gsh_dilate_batch(_ptr(dst), _ptr(src), w, h, n)
+
+    def morph_batch(self, dst, src, iterations, dilate, tmp=None):
+        """gsh_morph_batch: `iterations` applications of gs_erode (dilate false) / gs_dilate to src (n, h, w) uint8 in
+        ceil(iterations / 4) passes; tmp (n, h, w) uint8 or None = the library's scratch, used beyond 4 iterations"""
+        n, h, w = self._nhw(src)
+        self.c.gsh_morph_batch(_ptr(dst), _ptr(src), _ptr(tmp), w, h, n, 1 if dilate else 0, int(iterations))
 
     def histogram_batch(self, img, hist):
         n, h, w = self._nhw(img)

@@ -140,6 +140,53 @@ void launch_morph(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsi
   }
 }
 
+/* one pass of radius K = 2..4 (k_morphk.h) over frames that pass strip_ok; the band height of the short-band route is
+ * max(kMorphkBandRows[K], 4 K): each band first runs its 2 K halo rows through the horizontal step */
+constexpr unsigned kMorphkBandRows[5] = {0, 0, 16, 24, 32};
+template <bool DILATE, int K>
+void launch_morphk(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n) {
+  hipStream_t st = ctx().s();
+  const size_t fb = (size_t)w * h;
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const unsigned nn = std::min(kMaxZ, n - f0);
+    uint8_t *d = dst + fb * f0;
+    const uint8_t *s = src + fb * f0;
+    const int rg = strip_mode(w, s);
+    const StripCfg c = strip_cfg(w, h, nn, 5, 2 * K, kMorphkBandRows[K], rg);
+    if (rg == 1) GS_LAUNCH((k_morphk16<DILATE, K, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+    else if (rg == 2) GS_LAUNCH((k_morphk16<DILATE, K, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+    else GS_LAUNCH((k_morphk16<DILATE, K, 0>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+  }
+}
+/* `iterations` applications of the 3x3 operator as ceil(iterations / 4) passes: radius 4 while it fits, then the remainder
+ * 1..3 (1 is launch_morph).  The planes alternate so that the last pass writes dst and src is only read:
+ * src -> dst -> tmp -> dst ... for an odd pass count, src -> tmp -> dst ... for an even one.  Frames that fail strip_ok
+ * take one per-pixel launch of radius `iterations`, src -> dst. */
+template <bool DILATE>
+void launch_morph_iter(uint8_t *dst, const uint8_t *src, uint8_t *tmp, unsigned w, unsigned h, unsigned n, unsigned iterations) {
+  if (n == 0) return;
+  const size_t fb = (size_t)w * h;
+  if (!strip_ok(w, h)) {
+    if (iterations == 1) return launch_morph<DILATE>(dst, src, w, h, n);
+    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ)
+      GS_LAUNCH(k_morphr_px<DILATE>, grid2d(w, h, std::min(kMaxZ, n - f0)), dim3(64, 4), 0, ctx().s(), dst + fb * f0, src + fb * f0, w, h,
+                fb, iterations);
+    return;
+  }
+  const unsigned passes = (iterations + 3u) / 4u;
+  if (passes > 1 && !tmp) tmp = (uint8_t *)ctx().scratch(SL_AUX, fb * n);
+  const uint8_t *from = src;
+  for (unsigned p = 0, left = iterations; p < passes; p++) {
+    const unsigned k = left >= 4u ? 4u : left;
+    uint8_t *to = ((passes - p) & 1u) ? dst : tmp; /* the last pass (passes - p == 1) writes dst */
+    if (k == 4) launch_morphk<DILATE, 4>(to, from, w, h, n);
+    else if (k == 3) launch_morphk<DILATE, 3>(to, from, w, h, n);
+    else if (k == 2) launch_morphk<DILATE, 2>(to, from, w, h, n);
+    else launch_morph<DILATE>(to, from, w, h, n);
+    from = to, left -= k;
+  }
+}
+
 /* sq: the table of (p - 128)^2 (gs_match_template); only the banded form builds it -- false is returned, and nothing launched,
  * when this geometry would take the rows + columns form */
 bool launch_integral(const uint8_t *src, unsigned w, unsigned h, unsigned n, unsigned *ii, bool sq) {
@@ -470,6 +517,20 @@ void gsh_erode_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, u
 void gsh_dilate_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n) {
   GS_ASSERT(dst && src && w > 0 && h > 0);
   launch_morph<true>(dst, src, w, h, n);
+}
+void gsh_morph_batch(uint8_t *dst, const uint8_t *src, uint8_t *tmp, unsigned w, unsigned h, unsigned n, int dilate,
+                     unsigned iterations) {
+  GS_ASSERT(dst && src && w > 0 && h > 0);
+  GS_ASSERT(iterations >= 1);
+  if (n == 0) return;
+  const size_t nb = (size_t)w * h * n;
+  GS_ASSERT(dst + nb <= src || src + nb <= dst); /* dst is written while src is read */
+  if (tmp && iterations > 4) {                   /* the plane between two passes */
+    GS_ASSERT(tmp + nb <= dst || dst + nb <= tmp);
+    GS_ASSERT(tmp + nb <= src || src + nb <= tmp);
+  }
+  if (dilate) launch_morph_iter<true>(dst, src, tmp, w, h, n, iterations);
+  else launch_morph_iter<false>(dst, src, tmp, w, h, n, iterations);
 }
 
 /* ---------------------------------------------------------------- batch: histogram etc. */

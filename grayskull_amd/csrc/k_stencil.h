@@ -23,6 +23,7 @@
 #ifndef GS_K_STENCIL_H
 #define GS_K_STENCIL_H
 #include "k_strip.h"
+#include "k_morphk.h" /* k_morphk16<DILATE, K, RG>, K = 2..4, and k_morphr_px: iterated erode / dilate in one pass */
 
 namespace gs {
 

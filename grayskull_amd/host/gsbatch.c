@@ -6,11 +6,14 @@
  * i.e. every stage parses a header, allocates, runs and re-serialises the image.  This driver takes
  * the same verbs with the same arguments and the same validation, but
  *   - reads all inputs once, groups frames of equal size into batches,
- *   - uploads a batch once, keeps it in HBM between stages (two ping-pong planes),
+ *   - uploads a batch once, keeps it in HBM between stages (two ping-pong planes; a third one where a `morph` stage
+ *     of more than 4 iterations needs the plane between two of its passes),
  *   - runs every stage as one gsh_*_batch launch over the whole group (size-changing verbs: one
  *     stream-ordered gs_* call per frame on device pointers),
  *   - recognises `blur r : sobel [: threshold otsu]` (r = 1..3) and runs it through the fused
  *     one-pass kernels (gsh_blur_sobel_batch / gsh_edge_pipeline_batch),
+ *   - runs `morph <op> <n>` as ONE gsh_morph_batch call: ceil(n / 4) passes over the slice instead of n
+ *     (`morph dilate 9 : morph erode 10` is 6 passes, not 19; same bytes),
  *   - downloads once and writes the results.
  * Per file the output bytes are identical to piping the reference's nanomagick through the same
  * verbs (tests/test_gsbatch.py).
@@ -288,6 +291,7 @@ static unsigned stage_nblobs(const struct stage *s, unsigned w, unsigned h) {
 
 struct planes {
   uint8_t *cur, *other; /* device, each n * max frame bytes */
+  uint8_t *third;       /* same size: gsh_morph_batch's tmp; NULL unless the chain has a `morph` of more than 4 iterations */
   unsigned *hist;       /* n * 256 u32 */
   uint8_t *thr_dev;     /* n */
   uint8_t *thr_host;    /* n */
@@ -360,17 +364,10 @@ static void run_stages(const struct stage *st, int ns, struct planes *p, unsigne
         gsh_adaptive_threshold_batch(p->other, p->cur, w, h, n, (unsigned)s->a[0], s->a[1]);
         swap_planes(p);
         break;
-      case V_MORPH: {
-        int it;
-        for (it = 0; it < s->a[1]; it++) {
-          if (s->dilate)
-            gsh_dilate_batch(p->other, p->cur, w, h, n);
-          else
-            gsh_erode_batch(p->other, p->cur, w, h, n);
-          swap_planes(p);
-        }
+      case V_MORPH: /* nanomagick.c:110-135: n calls of the 3x3 operator = ceil(n / 4) passes of radius <= 4 */
+        gsh_morph_batch(p->other, p->cur, s->a[1] > 4 ? p->third : NULL, w, h, n, s->dilate, (unsigned)s->a[1]);
+        swap_planes(p);
         break;
-      }
       case V_RESIZE:
       case V_CROP: {
         unsigned ow = w, oh = h;
@@ -678,6 +675,9 @@ static void *worker(void *arg) {
     t0 = now_ms();
     p.cur = (uint8_t *)gsh_malloc(max_fb * cap);
     p.other = (uint8_t *)gsh_malloc(max_fb * cap);
+    p.third = NULL;
+    for (i = 0; i < ns; i++)
+      if (st[i].v == V_MORPH && st[i].a[1] > 4 && !p.third) p.third = (uint8_t *)gsh_malloc(max_fb * cap);
     p.hist = (unsigned *)gsh_malloc((size_t)cap * 256 * sizeof(unsigned));
     p.thr_dev = (uint8_t *)gsh_malloc(cap);
     p.thr_host = (uint8_t *)malloc(cap);
@@ -875,6 +875,7 @@ static void *worker(void *arg) {
       fprintf(stderr, "gpu %d group %d: %u of %u frame(s) %ux%u -> %ux%u\n", jb->device, g, n, ngroup, w, h, ow, oh);
     gsh_free(p.cur);
     gsh_free(p.other);
+    if (p.third) gsh_free(p.third);
     gsh_free(p.hist);
     gsh_free(p.thr_dev);
     gsh_free(p.labels);

@@ -117,6 +117,12 @@ void gsh_blur_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, un
 void gsh_sobel_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n);
 void gsh_erode_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n);
 void gsh_dilate_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n);
+/* `iterations` applications of gs_erode (dilate = 0) or gs_dilate (dilate != 0) to each of n frames, equal bit for bit to
+ * calling the 3x3 operator that many times (ref grayskull.h:286-304; nanomagick.c:110-135).  Runs ceil(iterations / 4)
+ * passes.  tmp: n*w*h bytes, used when more than one pass is needed; NULL = the library's own grow-only scratch
+ * (growing it synchronises once).  dst, src, tmp must not overlap; src is never written.  Stream-ordered. */
+void gsh_morph_batch(uint8_t *dst, const uint8_t *src, uint8_t *tmp, unsigned w, unsigned h, unsigned n,
+                     int dilate, unsigned iterations);
 
 /* ---- histogram / otsu / threshold (ref :199, :205, :225) ------------------------- */
 /* hist: n x 256 u32 (device).  thr: n x u8 (device). */
