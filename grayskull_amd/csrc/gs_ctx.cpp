@@ -144,4 +144,10 @@ void gsh_download(void *host, const void *dev, size_t bytes) {
 }
 int gsh_is_device_ptr(const void *p) { return is_dev(p) ? 1 : 0; }
 
+#ifdef GS_EMU
+static std::atomic<int> g_emu_device_pointers{0};
+void emu_device_pointers(int on) { g_emu_device_pointers.store(on != 0); }
+int emu_device_pointers_on(void) { return g_emu_device_pointers.load(); }
+#endif
+
 }  /* extern "C" */

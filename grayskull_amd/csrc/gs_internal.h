@@ -289,10 +289,18 @@ struct Ctx {
 };
 Ctx &ctx(); /* gs_ctx.cpp: one per calling thread */
 
+#ifdef GS_EMU
+/* Emulator builds only (the product library has neither symbol).  The emulator's gs_* calls normally take the staged
+ * (host pointer) path; emu_device_pointers(1) makes them take every non-NULL caller pointer for device memory, as the
+ * product does for hipMalloc'ed memory, so that a test can put a kernel straight onto a guarded buffer of its own
+ * (tests/guard_cases.py).  While on, gsh_is_device_ptr of an emulator build reports 1 for every non-NULL pointer too.
+ * Process-wide, off by default; defined in gs_ctx.cpp. */
+extern "C" void emu_device_pointers(int on);
+extern "C" int emu_device_pointers_on(void);
+#endif
 inline bool is_dev(const void *p) {
 #ifdef GS_EMU
-  (void)p;
-  return false;
+  return p && emu_device_pointers_on(); /* off: everything is staged */
 #else
   if (!p) return false;
   ctx().ensure_device();

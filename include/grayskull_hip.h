@@ -159,7 +159,7 @@ void gsh_cascade_destroy(gsh_cascade *dc);
 
 /* Per frame f: rects[f*max_rects ...] gets the first min(count,max_rects) detections in the
  * reference's (scale, y, x) order, counts[f] that number.  ii as produced by gsh_integral_batch.
- * rects/counts are device pointers.  Stream-ordered. */
+ * rects/counts are device pointers; records at and beyond counts[f] are not written.  Stream-ordered. */
 void gsh_lbp_detect_batch(const gsh_cascade *dc, const unsigned *ii, unsigned iw, unsigned ih,
                           unsigned n, struct gs_rect *rects, unsigned *counts, unsigned max_rects,
                           float scale_factor, float min_scale, float max_scale, int step);
@@ -180,18 +180,20 @@ uint64_t gsh_lbp_window_count(const struct gs_lbp_cascade *c, unsigned iw, unsig
  * ref :489); w, h >= 7 */
 void gsh_fast_score_batch(uint8_t *score, const uint8_t *img, unsigned w, unsigned h, unsigned n, unsigned threshold);
 /* kps: n*nkps records (device), counts: n (device).  scoremap: n frames; only the interior is
- * written, the 3-px frame is read by the NMS exactly like the reference does. */
+ * written, the 3-px frame is read by the NMS exactly like the reference does.  Frame f's first counts[f] records are
+ * written whole (angle and descriptor as 0, ref :530), the records at and beyond counts[f] are not written. */
 void gsh_fast_batch(const uint8_t *img, uint8_t *scoremap, unsigned w, unsigned h, unsigned n,
                     struct gs_keypoint *kps, unsigned *counts, unsigned nkps, unsigned threshold);
 
 /* Device image -> HOST keypoints.  Synchronous (orientation uses the host libm, like the
- * reference: grayskull.h:100-101).  Returns the number of keypoints written. */
+ * reference: grayskull.h:100-101).  Returns the number of keypoints written; the records behind them are not written. */
 unsigned gsh_orb_extract(const uint8_t *img_dev, unsigned w, unsigned h, uint8_t *scoremap_dev,
                          struct gs_keypoint *kps_host, unsigned nkps, unsigned threshold);
 
 /* gs_orb_extract for n frames of one size (frames w*h bytes apart): frame f's keypoints go to
  * kps_host[f*nkps ...], their number to counts_host[f].  scoremap_dev: n frames, same role as in
- * gsh_fast_batch.  Two host round trips for the whole batch.  Synchronous. */
+ * gsh_fast_batch.  Two host round trips for the whole batch.  Synchronous.  Records at and beyond counts_host[f] are
+ * not written. */
 void gsh_orb_extract_batch(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n,
                            uint8_t *scoremap_dev, struct gs_keypoint *kps_host, unsigned *counts_host,
                            unsigned nkps, unsigned threshold);
@@ -199,7 +201,8 @@ void gsh_orb_extract_batch(const uint8_t *img_dev, unsigned w, unsigned h, unsig
  * border filter, cap) and the trig run on the device.  The trig is the reference's GS_NO_STDLIB pair
  * (ref :70-88, the polynomials its wasm build uses), so results equal the reference header compiled
  * with -DGS_NO_STDLIB bit for bit -- angles and descriptors differ from the libm build's, like the
- * reference's own two builds differ.  kps_dev: n x nkps records, counts_dev: n; stream-ordered. */
+ * reference's own two builds differ.  kps_dev: n x nkps records, counts_dev: n; stream-ordered.  Records at and beyond
+ * counts_dev[f] are not written. */
 void gsh_orb_extract_batch_nostdlib(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n,
                                     uint8_t *scoremap_dev, struct gs_keypoint *kps_dev, unsigned *counts_dev,
                                     unsigned nkps, unsigned threshold);
@@ -209,13 +212,15 @@ void gsh_orb_extract_batch_nostdlib(const uint8_t *img_dev, unsigned w, unsigned
  * previous, stopping before a level narrower or lower than 32; nkps / n_levels keypoints per level
  * (the last level takes the remainder); coordinates scaled back by 2^level.  buffer_dev has the
  * reference's layout -- levels 1.. back to back, then one scoremap per level -- and its bytes are
- * the caller's (the NMS reads the never-written 3-px scoremap frames, ref :524).  Synchronous. */
+ * the caller's (the NMS reads the never-written 3-px scoremap frames, ref :524).  Synchronous.  Returns the number of
+ * keypoints written to kps_host; the records behind them are not written. */
 size_t gsh_orb_pyramid_buffer_bytes(unsigned w, unsigned h, unsigned n_levels);
 unsigned gsh_orb_extract_pyramid(const uint8_t *img_dev, unsigned w, unsigned h, uint8_t *buffer_dev,
                                  struct gs_keypoint *kps_host, unsigned nkps, unsigned threshold,
                                  unsigned n_levels);
 
-/* All pointers device; matches: max_matches records; count: 1 u32.  Stream-ordered. */
+/* All pointers device; matches: max_matches records, the first *count written, the rest not; count: 1 u32.
+ * Stream-ordered. */
 void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct gs_keypoint *k2,
                        unsigned n2, struct gs_match *matches, unsigned *count,
                        unsigned max_matches, float max_distance);
@@ -230,7 +235,8 @@ void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigne
 /* ---- connected components, blob corners, perspective correction (ref :330, :404, :423) ----------
  * The reference's document-scanner chain (blur -> Otsu threshold -> gs_blobs -> largest blob ->
  * gs_blob_corners -> gs_perspective_correct) on n same-size frames without a host round trip.
- * labels: n x w x h; blobs: n x nblobs records, frame f's first counts[f] written (the rest untouched);
+ * labels: n x w x h; blobs: n x nblobs records, frame f's first counts[f] written (all 32 bytes, the two padding bytes
+ * behind `label` as 0; the rest untouched);
  * counts: n.  Corners: blobs holds ONE record per frame (e.g. each frame's largest), corners n x 4
  * points {tl, tr, br, bl}; perspective: dst n x dw x dh from src n x sw x sh and n x 4 corners. */
 void gsh_blobs_batch(const uint8_t *img, unsigned w, unsigned h, unsigned n, gs_label *labels,
@@ -262,7 +268,8 @@ void gsh_blob_paint_batch(uint8_t *dst, const uint8_t *img, unsigned w, unsigned
  * later contour's length skips the pixels an earlier one marked.  Frames run side by side.  Of each record `start`
  * is read, `box` and `length` are written.  status[f * per_frame + k] (may be NULL): 0 the walk ended, 1 it is
  * endless in the reference (a state repeated; box, length and visited are the values it converges to), 2 the cap
- * on the moves of one walk was reached (a bug).  img and visited must not overlap.
+ * on the moves of one walk was reached (a bug).  Records and status bytes at and beyond counts[f] are not written.
+ * img and visited must not overlap.
  * gsh_blob_contour_starts_batch: for blob k < counts[f] of frame f (counts == NULL: all nblobs; labels, blobs,
  * counts as gsh_blobs_batch left them), contours[f * nblobs + k].start = the raster-first pixel that carries the
  * blob's label (it lies in row box.y, at x >= box.x); nothing else of the record is written. */
