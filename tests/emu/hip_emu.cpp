@@ -148,6 +148,83 @@ uint64_t quad_exchange(uint64_t v, unsigned sel) {
   return x.slot[buf][sel & 3u];
 }
 
+/* ---- schedules (see hip_emu.h) ---- */
+/* process-wide: the host thread pools of the batch entry points launch under it too.  The environment is read once, by
+ * whichever thread comes first (a function-local static: initialised under the language's own lock); set_schedule is
+ * called between launches, from the thread that drives the test. */
+static Schedule schedule_from_env() { /* GS_EMU_SCHEDULE=blocks,threads[,seed] */
+  Schedule s;
+  const char *e = getenv("GS_EMU_SCHEDULE");
+  if (!e || !*e) return s;
+  int b = 0, t = 0;
+  unsigned long long seed = 0;
+  const int n = sscanf(e, "%d,%d,%llu", &b, &t, &seed);
+  if (n < 2 || b < 0 || b > 3 || t < 0 || t > 3) {
+    fprintf(stderr, "emu: GS_EMU_SCHEDULE=%s is not blocks,threads[,seed] with kinds 0..3\n", e);
+    abort();
+  }
+  s.blocks = b, s.threads = t, s.seed = seed;
+  return s;
+}
+static Schedule &the_schedule() {
+  static Schedule s = schedule_from_env();
+  return s;
+}
+
+Schedule schedule() { return the_schedule(); }
+
+void set_schedule(int blocks, int threads, uint64_t seed) {
+  if (blocks < 0 || blocks > 3 || threads < 0 || threads > 3) {
+    fprintf(stderr, "emu: schedule kinds are 0..3 (got %d, %d)\n", blocks, threads);
+    abort();
+  }
+  Schedule &s = the_schedule(); /* an explicit call replaces what the environment selected */
+  s.blocks = blocks, s.threads = threads, s.seed = seed;
+  s.epoch++; /* every host thread restarts its launch counter: kind 3 is reproducible from here on */
+}
+
+/* splitmix64 over (seed, launch, block, round) */
+static uint64_t mix(uint64_t seed, uint64_t launch, uint64_t block, uint64_t round) {
+  uint64_t z = seed;
+  const uint64_t in[3] = {launch, block, round};
+  for (uint64_t v : in) {
+    z += 0x9e3779b97f4a7c15ull + v;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    z ^= z >> 31;
+  }
+  return z;
+}
+
+static uint64_t gcd64(uint64_t a, uint64_t b) {
+  while (b) {
+    const uint64_t r = a % b;
+    a = b, b = r;
+  }
+  return a;
+}
+
+/* position i of the order -> index in [0, n): no table, whatever the grid's size */
+struct Perm {
+  int kind;
+  uint64_t n, a = 1, b = 0;
+  Perm(int kind_, uint64_t n_, uint64_t key) : kind(kind_), n(n_) {
+    if (kind == 3 && n > 1) { /* affine map i -> (a i + b) mod n, a coprime to n */
+      a = 1 + key % (n - 1);
+      while (gcd64(a, n) != 1) a = a + 1 < n ? a + 1 : 1;
+      b = (key >> 32 | key << 32) % n;
+    }
+  }
+  uint64_t operator()(uint64_t i) const {
+    switch (kind) {
+      case 1: return n - 1 - i;
+      case 2: return (i & 1u) ? n - 1 - (i >> 1) : (i >> 1);
+      case 3: return (uint64_t)(((unsigned __int128)a * i + b) % n);
+      default: return i;
+    }
+  }
+};
+
 void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &body) {
   State &s = S();
   unsigned nt = block.x * block.y * block.z;
@@ -168,50 +245,68 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &bo
   s.quads.assign((nt + 3) / 4, State::QuadX());
   std::vector<char> lds(shmem + 16);
   s.dyn_lds = lds.data();
-  for (unsigned bz = 0; bz < grid.z; bz++)
-    for (unsigned by = 0; by < grid.y; by++)
-      for (unsigned bx = 0; bx < grid.x; bx++) {
-        s.bidx = {bx, by, bz};
-        s.bar_count = 0;
-        s.alive = nt;
-        for (auto &w : s.waves) {
-          w.count = 0;
-          w.alive = 0;
-          memset(w.valid, 0, sizeof w.valid);
-          memset(w.arrived, 0, sizeof w.arrived);
-          w.gen = 0;
-        }
-        for (auto &x : s.quads) x.count = 0;
-        for (unsigned t = 0; t < nt; t++) {
-          Fiber &f = s.fibers[t];
-          f.done = false;
-          f.started = false;
-          f.lin = t;
-          f.tid = {t % block.x, (t / block.x) % block.y, t / (block.x * block.y)};
-          s.waves[t / WAVE].alive++;
-          getcontext(&f.ctx);
-          f.ctx.uc_stack.ss_sp = f.stack;
-          f.ctx.uc_stack.ss_size = STACK;
-          f.ctx.uc_link = nullptr;
-          makecontext(&f.ctx, fiber_entry, 0);
-        }
-        unsigned long spins = 0;
-        while (s.alive > 0) {
-          for (unsigned t = 0; t < nt; t++) {
-            Fiber &f = s.fibers[t];
-            if (f.done) continue;
-            s.cur = (int)t;
-            s.tidx = f.tid;
-            hop(&s.sched, s.sched_jb, &f);
-          }
-          if (++spins > 50000000ul) {
-            fprintf(stderr, "emu: deadlock (divergent barrier / wave op?)\n");
-            abort();
-          }
-        }
+  /* the schedule of this launch: read once, so that a launch never changes order half way */
+  const Schedule sch = schedule();
+  if (s.sched_epoch != sch.epoch) s.sched_epoch = sch.epoch, s.launches = 0;
+  const uint64_t launch_no = s.launches++;
+  const uint64_t nblocks = (uint64_t)grid.x * grid.y * grid.z;
+  const Perm bperm(sch.blocks, nblocks, mix(sch.seed, launch_no, ~0ull, 0));
+  for (uint64_t bi = 0; bi < nblocks; bi++) {
+    /* kind 0 is the ascending (z, y, x) order of three nested loops */
+    const uint64_t b = bperm(bi);
+    const unsigned bx = (unsigned)(b % grid.x), by = (unsigned)(b / grid.x % grid.y), bz = (unsigned)(b / ((uint64_t)grid.x * grid.y));
+    s.bidx = {bx, by, bz};
+    s.bar_count = 0;
+    s.alive = nt;
+    for (auto &w : s.waves) {
+      w.count = 0;
+      w.alive = 0;
+      memset(w.valid, 0, sizeof w.valid);
+      memset(w.arrived, 0, sizeof w.arrived);
+      w.gen = 0;
+    }
+    for (auto &x : s.quads) x.count = 0;
+    for (unsigned t = 0; t < nt; t++) {
+      Fiber &f = s.fibers[t];
+      f.done = false;
+      f.started = false;
+      f.lin = t;
+      f.tid = {t % block.x, (t / block.x) % block.y, t / (block.x * block.y)};
+      s.waves[t / WAVE].alive++;
+      getcontext(&f.ctx);
+      f.ctx.uc_stack.ss_sp = f.stack;
+      f.ctx.uc_stack.ss_size = STACK;
+      f.ctx.uc_link = nullptr;
+      makecontext(&f.ctx, fiber_entry, 0);
+    }
+    unsigned long spins = 0;
+    while (s.alive > 0) {
+      /* one scheduling round: every live fiber is resumed once, in the order of the threads kind (kind 3: a new
+       * permutation per round, from the seed, the launch, the block and the round) */
+      const Perm tperm(sch.threads, nt, sch.threads == 3 ? mix(sch.seed, launch_no, b, spins) : 0);
+      for (unsigned k = 0; k < nt; k++) {
+        const unsigned t = sch.threads ? (unsigned)tperm(k) : k;
+        Fiber &f = s.fibers[t];
+        if (f.done) continue;
+        s.cur = (int)t;
+        s.tidx = f.tid;
+        hop(&s.sched, s.sched_jb, &f);
       }
+      if (++spins > 50000000ul) {
+        fprintf(stderr, "emu: deadlock (divergent barrier / wave op?)\n");
+        abort();
+      }
+    }
+  }
   s.cur = -1;
   s.body = nullptr;
 }
 
 }  // namespace emu
+
+/* the switch for tests that load the emulator library (ctypes): kinds as in hip_emu.h */
+extern "C" void emu_set_schedule(int blocks, int threads, unsigned long long seed) { emu::set_schedule(blocks, threads, seed); }
+extern "C" void emu_get_schedule(int *blocks, int *threads, unsigned long long *seed) {
+  const emu::Schedule s = emu::schedule();
+  *blocks = s.blocks, *threads = s.threads, *seed = s.seed;
+}

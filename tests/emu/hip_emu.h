@@ -4,8 +4,38 @@
  * There is no GPU in the build container, and GPU minutes are scarce, so the kernel
  * sources under grayskull_amd/csrc/ can also be compiled with g++ -DGS_EMU against this
  * header.  It runs one workgroup at a time; every work-item is a ucontext fiber, scheduled
- * round-robin on ONE OS thread, so runs are deterministic and race-free by construction.
- * Barriers and wave-level exchanges (ballot / DPP shift / shuffles) yield between fibers.
+ * round-robin on ONE OS thread, so a run is deterministic: the same schedule gives the same
+ * interleaving every time.  Barriers and wave-level exchanges (ballot / DPP shift /
+ * shuffles) yield between fibers.
+ *
+ * SCHEDULES.  Deterministic is not race-free: a run shows ONE interleaving, and a kernel
+ * whose result depends on the order of its blocks or waves is right or wrong under it by
+ * luck.  So the order is a switch (emu::set_schedule, emu_set_schedule() from outside the
+ * library, or GS_EMU_SCHEDULE=blocks,threads[,seed] in the environment), two independent
+ * orders with four kinds each:
+ *   blocks   the order in which a launch runs its workgroups, over the whole x*y*z grid
+ *   threads  the order in which each scheduling round resumes the live fibers of the
+ *            workgroup (this permutes the waves and the lanes inside a wave; the direct
+ *            hand-offs inside wave_rendezvous / quad_exchange stay as they are)
+ *   kind 0   ascending (the default; recorded digests and all tests without a schedule)
+ *   kind 1   descending
+ *   kind 2   outside-in: 0, n-1, 1, n-2, ...
+ *   kind 3   an affine permutation i -> (a i + b) mod n drawn from (seed, launch counter)
+ *            for the blocks, and from (seed, launch counter, block, round) for the threads:
+ *            a new one per launch / per round, reproducible, no memory proportional to n.
+ *            The launch counter is per host thread and restarts at every set_schedule.
+ * What the permuted schedules CAN show: a result that depends on the order in which blocks
+ * run (inter-block counters, "last block" protocols), on the order of the waves between two
+ * barriers, or on the order of the lanes between two wave operations (code that relies on
+ * lockstep execution).  What they still CANNOT show:
+ *   - two workgroups resident at once: blocks run one after the other, to completion
+ *     (__shared__ is one static thread_local per host thread), so a block never observes
+ *     another block half way;
+ *   - preemption between two memory operations: a fiber runs until its next barrier, wave
+ *     operation or exit, so a read-modify-write in plain C++ is never torn and the atomics
+ *     below are plain operations;
+ *   - streams: everything runs on the calling thread in call order, and the side-stream code
+ *     of the library is compiled out under GS_EMU.
  *
  * This checks INDEXING AND ARITHMETIC LOGIC of the kernels on tiny inputs.  It is not a
  * CPU fallback: the product library (libgrayskull_hip.so) never contains or loads it, and
@@ -88,11 +118,23 @@ struct State {
   std::vector<QuadX> quads;
   const std::function<void()> *body = nullptr;
   char *dyn_lds = nullptr;
+  /* launches of this host thread since the schedule was last set (kind 3 draws from it) */
+  uint64_t launches = 0;
+  unsigned sched_epoch = 0;
   ~State() { /* one State per host thread: give the fiber stacks back when the thread ends */
     for (auto &f : fibers) free(f.stack);
   }
 };
 State &S();
+
+/* the order of blocks and of threads (see SCHEDULES at the top): kinds 0..3 each */
+struct Schedule {
+  int blocks = 0, threads = 0;
+  uint64_t seed = 0;
+  unsigned epoch = 0; /* bumped by set_schedule */
+};
+Schedule schedule();
+void set_schedule(int blocks, int threads, uint64_t seed);
 
 void yield();
 void block_barrier();
@@ -132,7 +174,7 @@ auto emu::wave_exchange(uint64_t v, F fn) -> decltype(fn((const uint64_t *)0, (c
 #define GS_LAUNCH(kernel, grid, block, shmem, stream, ...) \
   emu::launch((grid), (block), (shmem), [=]() { kernel(__VA_ARGS__); })
 
-/* ---- atomics (single OS thread => plain ops are atomic) ---- */
+/* ---- atomics (single OS thread, no preemption inside a fiber => plain ops are atomic) ---- */
 template <class T> inline T atomicAdd(T *p, T v) { T o = *p; *p = o + v; return o; }
 template <class T> inline T atomicOr(T *p, T v) { T o = *p; *p = o | v; return o; }
 template <class T> inline T atomicMin(T *p, T v) { T o = *p; if (v < o) *p = v; return o; }
