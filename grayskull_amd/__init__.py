@@ -147,6 +147,11 @@ _SIGS = {
     "gsh_filter_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
                                 C.c_uint, C.c_uint, C.c_uint]),
     "gsh_downsample_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_crop_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, GsRect]),
+    "gsh_resize_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_resize_nn_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_crop_resize_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
+                                      C.c_void_p, C.c_uint, C.c_int]),
     "gsh_blobs_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_uint]),
     "gsh_blob_corners_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
@@ -559,6 +564,26 @@ class Grayskull:
     def downsample_batch(self, dst, src):
         n, h, w = self._nhw(src)
         self.c.gsh_downsample_batch(_ptr(dst), _ptr(src), w, h, n)
+
+    def crop_batch(self, dst, src, x, y, w, h):
+        """gsh_crop_batch: dst (n, h, w) = the window (x, y, w, h) of every frame of src (n, sh, sw) uint8"""
+        n, sh, sw = self._nhw(src)
+        self.c.gsh_crop_batch(_ptr(dst), _ptr(src), sw, sh, n, GsRect(x, y, w, h))
+
+    def resize_batch(self, dst, src, nearest=False):
+        """gsh_resize_batch / gsh_resize_nn_batch: dst (n, dh, dw) from src (n, sh, sw) uint8, frame by frame"""
+        n, sh, sw = self._nhw(src)
+        _, dh, dw = self._nhw(dst)
+        (self.c.gsh_resize_nn_batch if nearest else self.c.gsh_resize_batch)(_ptr(dst), dw, dh, _ptr(src), sw, sh, n)
+
+    def crop_resize_batch(self, dst, src, rois, frame_of=None, nearest=False):
+        """gsh_crop_resize_batch: dst (npatches, dh, dw) uint8; patch p = the window rois[p] = (x, y, w, h) of frame
+        frame_of[p] (frame p when frame_of is None) of src (n, sh, sw), resized; rois (npatches, 4) and frame_of
+        (npatches) int32 device tensors, read on the device"""
+        n, sh, sw = self._nhw(src)
+        npatches, dh, dw = self._nhw(dst)
+        self.c.gsh_crop_resize_batch(_ptr(dst), dw, dh, _ptr(src), sw, sh, n, _ptr(rois), _ptr(frame_of), npatches,
+                                     1 if nearest else 0)
 
     def blobs_batch(self, img, labels, blobs, counts, nblobs):
         """gsh_blobs_batch: img (n, h, w) uint8, labels (n, h, w) uint16 [or int16], blobs (n, nblobs, 8) int32 (one

@@ -10,6 +10,7 @@
 #include "k_geom.h"
 #include "k_integral.h"
 #include "k_pointwise.h"
+#include "k_resize.h"
 #include "k_stencil.h"
 #include "k_tmatch.h"
 
@@ -487,6 +488,74 @@ void launch_integral_pad(dim3 grid, hipStream_t st, const unsigned *ii, unsigned
   GS_LAUNCH(k_integral_pad, grid, dim3(64, 4), 0, st, ii, w, h, padded);
 }
 
+/* ---------------------------------------------------------------- geometry: crop, resize, patches (k_resize.h)
+ * One kernel family for the batch entries and the drop-in calls (n = 1).
+ * k_resize_tile stages a block's source rectangle in LDS where that pays and fits and gathers from global memory where
+ * not; the block decides from the window and the rectangle it computes, the launcher only sizes the LDS and the band:
+ *   whole frames: more than four source pixels per result pixel (sw sh > 4 dw dh): no LDS, every block gathers (staged
+ *     against gathered, ms: 64 x 4K to 640x360 0.228 against 0.044, to 1279x719 0.233 against 0.162, 512 x 612x816 to
+ *     300x400 0.264 against 0.241 -- but 64 x 4K to 1920x1080 0.266 against 0.343 and 256 x 720p to 1080p 0.51 against
+ *     0.97; profiles/geom_batch.json).  Else the rectangle of 256 columns x `band` rows is at most E(256, sw, dw) x
+ *     E(band, sh, dh) source pixels, E(c, s, d) = min(s, ceil(c s / d) + 3): the largest band of 16, 8, 4 rows whose
+ *     rectangle fits kResizeLdsSmall (several blocks per CU); else 4 rows if they fit kResizeLdsMax; else no LDS.
+ *   windows read on the device (gsh_crop_resize_batch): kResizeLdsSmall and bands of 16 rows; a block whose window is
+ *     too large for that gathers.
+ * GSH_TUNE_GEOM_FORM = 1 gives no LDS at all (the gather form everywhere), 2 stages whatever the scale wherever the
+ * rectangle fits (both for A/B measurements). */
+constexpr unsigned kResizeLdsSmall = 16u * 1024u, kResizeLdsMax = 48u * 1024u;
+static unsigned resize_extent(unsigned c, unsigned s, unsigned d) {
+  return (unsigned)std::min<unsigned long long>(s, ((unsigned long long)c * s + d - 1) / d + 3);
+}
+struct ResizePlan { unsigned band, lds; };
+static ResizePlan resize_plan(unsigned dw, unsigned dh, unsigned sw, unsigned sh, bool windows) {
+  ResizePlan pl = {16u, 0u};
+  const bool dense = (unsigned long long)sw * sh <= 4ull * dw * dh || g_tune[25] == 2;
+  if (g_tune[25] != 1 && (windows || dense)) {
+    if (windows) {
+      pl.lds = kResizeLdsSmall;
+    } else {
+      const unsigned pitch = (resize_extent(std::min(dw, 256u), sw, dw) + 3u) & ~3u;
+      for (unsigned band = 16; band >= 4 && !pl.lds; band >>= 1) {
+        const unsigned long long need = (unsigned long long)pitch * resize_extent(std::min(band, dh), sh, dh);
+        if (need <= (band > 4 ? kResizeLdsSmall : kResizeLdsMax)) pl.band = band, pl.lds = (unsigned)need;
+      }
+    }
+  }
+  if ((dh + pl.band - 1) / pl.band > 65535u) pl.band = (((dh + 65534u) / 65535u) + 3u) & ~3u; /* grid.y; such a block gathers */
+  return pl;
+}
+/* count patches (rois == NULL: the n whole frames) of dw x dh from n frames of sw x sh */
+static void launch_resize(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n,
+                          const unsigned *rois, const unsigned *frame_of, unsigned count, bool nearest) {
+  const ResizePlan pl = resize_plan(dw, dh, sw, sh, rois != nullptr);
+  ResizeArgs a;
+  a.dst = dst, a.src = src, a.rois = rois, a.frame_of = frame_of;
+  a.dw = dw, a.dh = dh, a.sw = sw, a.sh = sh, a.n = n;
+  a.band = pl.band, a.lds = pl.lds, a.any_density = g_tune[25] == 2 ? 1u : 0u;
+  const bool nt = (unsigned long long)dw * dh * count > (256ull << 20); /* beyond the Infinity Cache: streaming stores */
+  hipStream_t st = ctx().s();
+  for (unsigned f0 = 0; f0 < count; f0 += kMaxZ) {
+    const dim3 grid((dw + 255) / 256, (dh + pl.band - 1) / pl.band, std::min(kMaxZ, count - f0));
+    a.z0 = f0;
+    if (nearest && nt) GS_LAUNCH((k_resize_tile<true, true>), grid, dim3(64, 4), pl.lds, st, a);
+    else if (nearest) GS_LAUNCH((k_resize_tile<true, false>), grid, dim3(64, 4), pl.lds, st, a);
+    else if (nt) GS_LAUNCH((k_resize_tile<false, true>), grid, dim3(64, 4), pl.lds, st, a);
+    else GS_LAUNCH((k_resize_tile<false, false>), grid, dim3(64, 4), pl.lds, st, a);
+  }
+}
+static void launch_crop(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n, struct gs_rect roi) {
+  GS_ASSERT(roi.x <= sw && roi.w <= sw - roi.x && roi.y <= sh && roi.h <= sh - roi.y); /* inside the frame, no 32-bit wrap */
+  const size_t sfb = (size_t)sw * sh, dfb = (size_t)roi.w * roi.h;
+  const bool nt = (unsigned long long)dfb * n > (256ull << 20);
+  hipStream_t st = ctx().s();
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const dim3 grid(((roi.w + 15) / 16 + 63) / 64, (roi.h + 3) / 4, std::min(kMaxZ, n - f0));
+    if (nt) GS_LAUNCH(k_crop_rows<true>, grid, dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh, roi.x, roi.y, roi.w, roi.h);
+    else GS_LAUNCH(k_crop_rows<false>, grid, dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh, roi.x, roi.y, roi.w, roi.h);
+  }
+}
+static bool apart(const uint8_t *a, size_t na, const uint8_t *b, size_t nb) { return a + na <= b || b + nb <= a; }
+
 }  // namespace gsi
 
 extern "C" {
@@ -771,6 +840,34 @@ void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigne
   }
 }
 
+void gsh_crop_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n, struct gs_rect roi) {
+  if (n == 0) return;
+  GS_ASSERT(dst && src && sw > 0 && sh > 0 && roi.w > 0 && roi.h > 0);
+  GS_ASSERT(roi.x <= sw && roi.w <= sw - roi.x && roi.y <= sh && roi.h <= sh - roi.y); /* ref :155, without the wrap of x + w */
+  GS_ASSERT(apart(dst, (size_t)roi.w * roi.h * n, src, (size_t)sw * sh * n));
+  launch_crop(dst, src, sw, sh, n, roi);
+}
+static void resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n,
+                         bool nearest) {
+  if (n == 0) return;
+  GS_ASSERT(dst && src && dw > 0 && dh > 0 && sw > 0 && sh > 0);
+  GS_ASSERT(apart(dst, (size_t)dw * dh * n, src, (size_t)sw * sh * n));
+  launch_resize(dst, dw, dh, src, sw, sh, n, nullptr, nullptr, n, nearest);
+}
+void gsh_resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n) {
+  resize_batch(dst, dw, dh, src, sw, sh, n, false);
+}
+void gsh_resize_nn_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n) {
+  resize_batch(dst, dw, dh, src, sw, sh, n, true);
+}
+void gsh_crop_resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n,
+                           const struct gs_rect *rois_dev, const unsigned *frame_of_dev, unsigned npatches, int nearest) {
+  if (n == 0 || npatches == 0) return;
+  GS_ASSERT(dst && src && rois_dev && dw > 0 && dh > 0 && sw > 0 && sh > 0);
+  GS_ASSERT(apart(dst, (size_t)dw * dh * npatches, src, (size_t)sw * sh * n));
+  launch_resize(dst, dw, dh, src, sw, sh, n, (const unsigned *)rois_dev, frame_of_dev, npatches, nearest != 0);
+}
+
 /* ---------------------------------------------------------------- synthetic frames, checksums */
 void gsh_synth_batch(uint8_t *dst, unsigned w, unsigned h, unsigned n, uint32_t seed0) {
   GS_ASSERT(dst && w > 0 && h > 0);
@@ -915,8 +1012,11 @@ void gs_crop(struct gs_image dst, struct gs_image src, struct gs_rect roi) { /* 
   const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
   const bool dhost = !is_dev(dst.data);
   uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, db) : dst.data;
-  GS_LAUNCH(k_crop, dim3((roi.w + 63) / 64, (roi.h + 3) / 4), dim3(64, 4), 0, ctx().s(), d, dst.w, dst.h, s,
-            src.w, src.h, roi.x, roi.y, roi.w, roi.h);
+  if (roi.x <= src.w && roi.w <= src.w - roi.x && roi.y <= src.h && roi.h <= src.h - roi.y)
+    launch_crop(d, s, src.w, src.h, 1, roi);
+  else /* accepted only because the reference's sums wrap: its gs_get semantics pixel by pixel */
+    GS_LAUNCH(k_crop_wrapped, dim3((roi.w + 63) / 64, (roi.h + 3) / 4), dim3(64, 4), 0, ctx().s(), d, s, src.w, src.h, roi.x,
+              roi.y, roi.w, roi.h);
   if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, db, hipMemcpyDeviceToHost, ctx().s()));
   finish(dhost);
 }
@@ -929,9 +1029,7 @@ static void resize_common(struct gs_image dst, struct gs_image src, bool nearest
   const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
   const bool dhost = !is_dev(dst.data);
   uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, db) : dst.data;
-  const dim3 g((dst.w + 63) / 64, (dst.h + 3) / 4);
-  if (nearest) GS_LAUNCH(k_resize_nn, g, dim3(64, 4), 0, ctx().s(), d, dst.w, dst.h, s, src.w, src.h);
-  else GS_LAUNCH(k_resize, g, dim3(64, 4), 0, ctx().s(), d, dst.w, dst.h, s, src.w, src.h);
+  launch_resize(d, dst.w, dst.h, s, src.w, src.h, 1, nullptr, nullptr, 1, nearest);
   if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, db, hipMemcpyDeviceToHost, ctx().s()));
   finish(dhost);
 }

@@ -1,8 +1,7 @@
 /*
- * k_geom.h -- SURVEY.md 8(f) rank 4: gs_crop / gs_copy (grayskull.h:154-162), gs_resize_nn (:164-169),
- * gs_resize (:171-187), gs_match_template (:705-724), gs_find_best_match (:726-739).
- * One thread per output pixel; byte accesses coalesce along x.  Not tuned: none of BASELINE.json's
- * configurations is bounded by them.
+ * k_geom.h -- SURVEY.md 8(f) rank 4: gs_match_template (grayskull.h:705-724) and gs_find_best_match (:726-739).
+ * (gs_crop / gs_copy, gs_resize_nn and gs_resize live in k_resize.h; the matrix-core template match in k_tmatch.h.)
+ * One thread per result pixel -- four in k_match_template4 --, blocks of 64 x 4.
  */
 #ifndef GS_K_GEOM_H
 #define GS_K_GEOM_H
@@ -13,48 +12,6 @@ namespace gs {
 /* gs_get (ref :143-145): 0 outside the image */
 GS_DEV unsigned geom_px(const uint8_t *img, unsigned w, unsigned h, unsigned x, unsigned y) {
   return (x < w && y < h) ? img[(size_t)y * w + x] : 0u;
-}
-
-/* grid (ceil(rw/64), ceil(rh/4)), block (64,4): dst(x,y) = src(rx+x, ry+y), dropped outside dst */
-__global__ __launch_bounds__(256) void k_crop(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src,
-                                              unsigned sw, unsigned sh, unsigned rx, unsigned ry,
-                                              unsigned rw, unsigned rh) {
-  const unsigned x = blockIdx.x * 64u + threadIdx.x, y = blockIdx.y * 4u + threadIdx.y;
-  if (x >= rw || y >= rh || x >= dw || y >= dh) return;
-  dst[(size_t)y * dw + x] = (uint8_t)geom_px(src, sw, sh, rx + x, ry + y);
-}
-
-/* NN: the reference's unsigned index arithmetic (x * sw wraps like its u32 does) */
-__global__ __launch_bounds__(256) void k_resize_nn(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src,
-                                                   unsigned sw, unsigned sh) {
-  const unsigned x = blockIdx.x * 64u + threadIdx.x, y = blockIdx.y * 4u + threadIdx.y;
-  if (x >= dw || y >= dh) return;
-  const unsigned sx = x * sw / dw, sy = y * sh / dh;
-  dst[(size_t)y * dw + x] = (uint8_t)geom_px(src, sw, sh, sx, sy);
-}
-
-/* bilinear: float32, operation for operation like ref :173-185 (no FMA contraction: the library is
- * built -ffp-contract=off); unsigned -> float conversions where the reference's C has them */
-__global__ __launch_bounds__(256) void k_resize(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src,
-                                                unsigned sw, unsigned sh) {
-#ifndef GS_EMU
-#pragma clang fp contract(off)
-#endif
-  const unsigned x = blockIdx.x * 64u + threadIdx.x, y = blockIdx.y * 4u + threadIdx.y;
-  if (x >= dw || y >= dh) return;
-  float sx = ((float)x + 0.5f) * (float)sw / (float)dw - 0.5f;
-  float sy = ((float)y + 0.5f) * (float)sh / (float)dh - 0.5f;
-  const float mx = (float)sw - 1.0f, my = (float)sh - 1.0f;
-  sx = sx < mx ? sx : mx, sx = 0.0f > sx ? 0.0f : sx;
-  sy = sy < my ? sy : my, sy = 0.0f > sy ? 0.0f : sy;
-  const unsigned xi = (unsigned)sx, yi = (unsigned)sy;
-  const unsigned x1 = xi + 1 < sw - 1 ? xi + 1 : sw - 1, y1 = yi + 1 < sh - 1 ? yi + 1 : sh - 1;
-  const float dx = sx - (float)xi, dy = sy - (float)yi;
-  const int c00 = (int)geom_px(src, sw, sh, xi, yi), c01 = (int)geom_px(src, sw, sh, x1, yi);
-  const int c10 = (int)geom_px(src, sw, sh, xi, y1), c11 = (int)geom_px(src, sw, sh, x1, y1);
-  const float p = ((float)c00 * (1 - dx) * (1 - dy)) + ((float)c01 * dx * (1 - dy)) +
-                  ((float)c10 * (1 - dx) * dy) + ((float)c11 * dx * dy);
-  dst[(size_t)y * dw + x] = (uint8_t)(int)p; /* float -> uint8_t truncation (value < 256) */
 }
 
 /* sum of squares of n bytes into *out (one block of 256; the template's constant term) */

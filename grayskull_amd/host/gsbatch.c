@@ -8,8 +8,8 @@
  *   - reads all inputs once, groups frames of equal size into batches,
  *   - uploads a batch once, keeps it in HBM between stages (two ping-pong planes; a third one where a `morph` stage
  *     of more than 4 iterations needs the plane between two of its passes),
- *   - runs every stage as one gsh_*_batch launch over the whole group (size-changing verbs: one
- *     stream-ordered gs_* call per frame on device pointers),
+ *   - runs every stage as one gsh_*_batch launch over the whole group (the size-changing verbs too: gsh_resize_batch /
+ *     gsh_crop_batch),
  *   - recognises `blur r : sobel [: threshold otsu]` (r = 1..3) and runs it through the fused
  *     one-pass kernels (gsh_blur_sobel_batch / gsh_edge_pipeline_batch),
  *   - runs `morph <op> <n>` as ONE gsh_morph_batch call: ceil(n / 4) passes over the slice instead of n
@@ -372,15 +372,11 @@ static void run_stages(const struct stage *st, int ns, struct planes *p, unsigne
       case V_CROP: {
         unsigned ow = w, oh = h;
         stage_out_size(s, &ow, &oh);
-        for (f = 0; f < n; f++) {
-          struct gs_image src = {w, h, p->cur + fb * f};
-          struct gs_image dst = {ow, oh, p->other + (size_t)ow * oh * f};
-          if (s->v == V_RESIZE) {
-            gs_resize(dst, src);
-          } else {
-            struct gs_rect roi = {(unsigned)s->a[0], (unsigned)s->a[1], (unsigned)s->a[2], (unsigned)s->a[3]};
-            gs_crop(dst, src, roi);
-          }
+        if (s->v == V_RESIZE) {
+          gsh_resize_batch(p->other, ow, oh, p->cur, w, h, n);
+        } else {
+          struct gs_rect roi = {(unsigned)s->a[0], (unsigned)s->a[1], (unsigned)s->a[2], (unsigned)s->a[3]};
+          gsh_crop_batch(p->other, p->cur, w, h, n, roi);
         }
         w = ow;
         h = oh;
@@ -566,7 +562,7 @@ static void *worker(void *arg) {
   const double t_start = now_ms();
   memset(&mine, 0, sizeof mine);
   gsh_set_device(jb->device);
-  gsh_set_async(1); /* per-frame gs_resize / gs_crop on device pointers stay stream-ordered */
+  gsh_set_async(1); /* every stage is a stream-ordered gsh_*_batch call; a drop-in gs_* call on device pointers would stay stream-ordered too */
   if (term && term->v == V_FACES) {
     /* SURVEY 8(e) collective (1): rank 0 read the blob; its length travels as an all-reduce(max), its bytes as one
      * broadcast; every rank -- rank 0 included -- builds its device tables from the bytes it received */

@@ -81,7 +81,9 @@ enum gsh_tune_key {
   GSH_TUNE_RETIRED_21 = 21,       /* retired (round 3's rule for the strip kernels) */
   GSH_TUNE_EXPERIMENT_22 = 22,    /* GS_EXPERIMENT builds only: gs_sobel without the reads that preserve columns 0 / w-1 */
   GSH_TUNE_EXPERIMENT_23 = 23,    /* GS_EXPERIMENT builds only: the strip-copy probe keeps the stencils' halo load */
-  GSH_TUNE_RETIRED_24 = 24        /* retired (realigning strip flavour never / always) */
+  GSH_TUNE_RETIRED_24 = 24,       /* retired (realigning strip flavour never / always) */
+  GSH_TUNE_GEOM_FORM = 25         /* the resize kernels: 1 gather every tap from global memory (no LDS staging), 2 stage the source
+                                     rectangle wherever it fits the LDS, also beyond four source pixels per result pixel */
 };
 void gsh_tune(int key, int value);
 /* measurement aid for bench.py: while on, gsh_edge_pipeline_batch brackets every launch of its
@@ -231,6 +233,26 @@ void gsh_adaptive_threshold_batch(uint8_t *dst, const uint8_t *src, unsigned w, 
 void gsh_filter_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n,
                       const int8_t *kernel_host, unsigned kw, unsigned kh, unsigned norm);
 void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n);
+
+/* ---- geometry on batches and patches (ref :154-187; docs/design/stencils.md "Geometry") ------------
+ * Frames dense and back to back (sw * sh resp. dw * dh bytes apart), all pointers device pointers, stream-ordered on the
+ * current stream: no host synchronisation, no allocation, no table built on the host, no read-back.  n == 0 (or
+ * npatches == 0) returns before any check or launch.  Sizes are non-zero, the roi of gsh_crop_batch lies inside the frame
+ * and dst does not overlap src (GS_ASSERT).  Results are the reference's, frame by frame and bit for bit:
+ *   gsh_crop_batch        frame f = gs_crop(dst_f, src_f, roi), dst frames roi.w x roi.h
+ *   gsh_resize_batch      frame f = gs_resize(dst_f, src_f);  gsh_resize_nn_batch: gs_resize_nn
+ *   gsh_crop_resize_batch patch p (dw x dh) = gs_resize -- gs_resize_nn when `nearest` -- of the image gs_crop gives for
+ *                         rois_dev[p] of frame frame_of_dev[p] (frame p when frame_of_dev is NULL): the bilinear taps
+ *                         clamp at the WINDOW's edges.  rois_dev and frame_of_dev are read on the device, e.g. as
+ *                         gsh_lbp_detect_batch or gsh_blob_largest_batch left them; nothing can assert there, so a patch
+ *                         whose rectangle is empty or does not lie inside the frame (x + w is tested without 32-bit
+ *                         overflow) or whose frame index is >= n is filled with zeros, and nothing else is touched. */
+void gsh_crop_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n, struct gs_rect roi);
+void gsh_resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n);
+void gsh_resize_nn_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n);
+void gsh_crop_resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n,
+                           const struct gs_rect *rois_dev, const unsigned *frame_of_dev /* NULL: patch p comes from frame p */,
+                           unsigned npatches, int nearest);
 
 /* ---- connected components, blob corners, perspective correction (ref :330, :404, :423) ----------
  * The reference's document-scanner chain (blur -> Otsu threshold -> gs_blobs -> largest blob ->
