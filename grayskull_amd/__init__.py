@@ -152,6 +152,11 @@ _SIGS = {
     "gsh_resize_nn_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
     "gsh_crop_resize_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
                                       C.c_void_p, C.c_uint, C.c_int]),
+    "gsh_match_template_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                         C.c_void_p]),
+    "gsh_find_best_match_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
+    "gsh_locate_template_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                          C.c_void_p, C.c_void_p]),
     "gsh_blobs_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_uint]),
     "gsh_blob_corners_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
@@ -584,6 +589,34 @@ class Grayskull:
         npatches, dh, dw = self._nhw(dst)
         self.c.gsh_crop_resize_batch(_ptr(dst), dw, dh, _ptr(src), sw, sh, n, _ptr(rois), _ptr(frame_of), npatches,
                                      1 if nearest else 0)
+
+    @staticmethod
+    def _templates(tmpl, n):
+        """(tw, th, ntmpl) of one (th, tw) template for every frame or of n templates (n, th, tw)"""
+        if tmpl.ndim == 2:
+            return int(tmpl.shape[1]), int(tmpl.shape[0]), 1
+        if tmpl.ndim != 3:
+            raise ValueError("expected a (th, tw) or an (n, th, tw) uint8 template")
+        return int(tmpl.shape[2]), int(tmpl.shape[1]), int(tmpl.shape[0])
+
+    def match_template_batch(self, result, img, tmpl):
+        """gsh_match_template_batch: result (n, ih - th + 1, iw - tw + 1) = gs_match_template of every frame of img
+        (n, ih, iw) uint8 against tmpl (th, tw) -- one for all -- or tmpl (n, th, tw) -- template f for frame f"""
+        n, ih, iw = self._nhw(img)
+        tw, th, ntmpl = self._templates(tmpl, n)
+        self.c.gsh_match_template_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, ntmpl, _ptr(result))
+
+    def find_best_match_batch(self, result, best, score=None):
+        """gsh_find_best_match_batch: best (n, 2) int32 {x, y} = gs_find_best_match of every map of result (n, rh, rw)
+        uint8, score (n) uint8 or None the map's value there -- device tensors, nothing comes back to the host"""
+        n, rh, rw = self._nhw(result)
+        self.c.gsh_find_best_match_batch(_ptr(result), rw, rh, n, _ptr(best), _ptr(score))
+
+    def locate_template_batch(self, img, tmpl, best, score=None):
+        """gsh_locate_template_batch: match_template_batch + find_best_match_batch without a result map"""
+        n, ih, iw = self._nhw(img)
+        tw, th, ntmpl = self._templates(tmpl, n)
+        self.c.gsh_locate_template_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, ntmpl, _ptr(best), _ptr(score))
 
     def blobs_batch(self, img, labels, blobs, counts, nblobs):
         """gsh_blobs_batch: img (n, h, w) uint8, labels (n, h, w) uint16 [or int16], blobs (n, nblobs, 8) int32 (one

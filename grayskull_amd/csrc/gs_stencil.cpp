@@ -556,6 +556,181 @@ static void launch_crop(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned 
 }
 static bool apart(const uint8_t *a, size_t na, const uint8_t *b, size_t nb) { return a + na <= b || b + nb <= a; }
 
+/* ---- template matching: ONE launcher for gs_match_template (a launch of one frame) and the batch entries ------------------ */
+/* the form of k_match_template_mfma for a launch of `frames` frames */
+struct TmForm {
+  bool split, band;
+  unsigned istride;
+  size_t lds;
+};
+static TmForm tm_form(unsigned tw, unsigned th, unsigned rw, unsigned rh, unsigned frames) {
+  TmForm f;
+  const unsigned nkc = (tw + 31 + 31) / 32;
+  /* few 64 x 128 tiles: 32 x 64 tiles, the template rows split over the block's four waves.  The rule counts the blocks of
+   * the WHOLE launch, tiles per frame times frames: a 720p frame alone has 120 whole tiles for 256 CUs, five of them fill
+   * the chip.  key 20 = 8: 64 x 128 tiles, banded, whatever the size */
+  f.split = g_tune[20] == 3 || (g_tune[20] != 2 && g_tune[20] != 8 && (unsigned long long)((rw + 127) / 128) * ((rh + 63) / 64) * frames < 512);
+  f.istride = (f.split ? 32 : 96) + 32 * nkc + 16;
+  /* SPLIT = 1 takes templates taller than a band kTmBand rows at a time (k_tmatch.h BAND: 33 KB of LDS per block instead of 79 at
+   * 128 x 128, four blocks per CU); key 20 = 2: the whole template resident, as in round 3 */
+  f.band = !f.split && g_tune[20] != 2 && th > kTmBand;
+  const unsigned rows = f.band ? kTmBand : th;
+  f.lds = std::max<size_t>((size_t)((f.split ? 31 : 63) + rows) * f.istride + (size_t)rows * (32 * nkc + 48) + 16, f.split ? 32768 : 0);
+  return f;
+}
+/* templates of 512 .. 32768 taps, 16 .. 257 wide, whose block fits the LDS: the cross term on the matrix cores (k_tmatch.h;
+ * smaller ones are as fast on the dot-product kernels: 1280x720, 16 x 16: 39 vs 47 us).
+ * gsh_tune key 20 = 1: the VALU dot-product kernels; 2 / 3: always 64 x 128 tiles / always 32 x 64 tiles with split rows.
+ * The route is a property of ONE frame's geometry -- a batch takes, frame by frame, the route gs_match_template takes for a frame
+ * of that size; only the tile form looks at the launch (tm_form). */
+enum TmRoute { TM_MFMA, TM_DOT, TM_PX };
+static TmRoute tm_route(unsigned iw, unsigned ih, unsigned tw, unsigned th) {
+  const size_t ib = (size_t)iw * ih, tb = (size_t)tw * th;
+  const unsigned nkc = (tw + 31 + 31) / 32;
+  const TmForm one = tm_form(tw, th, iw - tw + 1, ih - th + 1, 1);
+  if (g_tune[20] != 1 && tw >= 16 && nkc <= 9 && th >= 4 && (tb >= 512 || g_tune[20] == 2 || g_tune[20] == 3 || g_tune[20] == 8) && tb <= 32768 &&
+      one.lds <= 150 * 1024 && ib < 0x7fffffffull)
+    return TM_MFMA;
+  return tw <= kTmplTile - 3 ? TM_DOT : TM_PX;
+}
+/* The batch entries work through their frames in chunks so that the context scratch stays below kTmScratchBudget however
+ * many frames a call brings: the matrix-core route keeps a u32 prefix table (ih (iw + 1) entries) and the u32 window sums
+ * (rw rh entries) per frame -- 7.2 MB for a 720p frame, 66 MB for a 4K one --, the other routes a result map per frame
+ * when they locate.  128 MiB: half the Infinity Cache, so that what one pass of a chunk writes the next still finds there;
+ * 18 frames of 720p (about 2000 whole tiles) or two 4K frames (1900).  A frame that alone needs more is a chunk of its own, as it
+ * is for gs_match_template.  gsh_tune key 26 caps the frames of a chunk (test hook). */
+constexpr size_t kTmScratchBudget = (size_t)128 << 20;
+static unsigned tm_chunk_frames(TmRoute route, unsigned iw, unsigned ih, unsigned rw, unsigned rh, unsigned n, bool locate) {
+  const size_t per = route == TM_MFMA ? ((size_t)ih * (iw + 1) + (size_t)rw * rh) * 4 : locate ? (size_t)rw * rh : 0;
+  size_t c = std::min<size_t>(n, kMaxZ);
+  if (per) c = std::min(c, std::max<size_t>(1, kTmScratchBudget / per));
+  if (g_tune[26] > 0) c = std::min<size_t>(c, (size_t)g_tune[26]);
+  return (unsigned)c;
+}
+/* nn frames (iw x ih, back to back) against one template (ntmpl == 1) or template f for frame f (ntmpl == nn) in one set of
+ * launches on the current stream.  d: the nn result maps; d == nullptr (matrix-core route only): the locate epilogue, keys[f]
+ * (zeroed, stream-ordered, before this call) receives frame f's best key. */
+static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, const uint8_t *t, unsigned tw, unsigned th, unsigned ntmpl,
+                      uint8_t *d, unsigned long long *keys) {
+  const unsigned rw = iw - tw + 1, rh = ih - th + 1;
+  const size_t ib = (size_t)iw * ih, tb = (size_t)tw * th, rb = (size_t)rw * rh;
+  const TmRoute route = tm_route(iw, ih, tw, th);
+  hipStream_t st = ctx().s();
+  if (route == TM_MFMA) {
+    TmForm f = tm_form(tw, th, rw, rh, nn);
+    if (f.lds > 150 * 1024) f = tm_form(tw, th, rw, rh, 1); /* the form one frame takes fits (tm_route) */
+    const bool tm_split = f.split, tm_band = f.band;
+    const unsigned nkc = (tw + 31 + 31) / 32, istride = f.istride, tstride = 32 * nkc + 48;
+    const size_t tm_lds = f.lds, tpb = (size_t)th * tstride; /* tstride is a multiple of 16 */
+    unsigned *rowp = (unsigned *)ctx().scratch(SL_II, (size_t)nn * ih * (iw + 1) * 4);
+    unsigned *s2 = (unsigned *)ctx().scratch(SL_PAD, (size_t)nn * rb * 4);
+    uint8_t *tpad = (uint8_t *)ctx().scratch(SL_PRE, ntmpl * tpb + (size_t)ntmpl * 4 + 16);
+    unsigned *tsqp = (unsigned *)(tpad + ((ntmpl * tpb + 3) & ~(size_t)3));
+    GS_LAUNCH(k_tm_prep, dim3(ntmpl), dim3(1024), 0, st, t, tw, th, tstride, tpad, tsqp);
+    /* window sums of (I - 128)^2: four corners of the banded integral table of squares (round 4) for frames of 4 Mpx and
+     * more -- 4K, 128 x 128: 0.269 -> 0.249 ms, 64 x 64: 0.135 -> 0.125; on a 720p frame the four short launches are 6-10 us
+     * SLOWER than the two passes of round 3 (row prefix + sliding columns), which stay for small frames, for key 20 = 4 and
+     * for geometries the banded integral does not take (key 20 = 5: the table route whatever the size);
+     * profiles/r04v_match_template_integral_squares.log */
+    if (g_tune[20] != 4 && (ib >= (4u << 20) || g_tune[20] == 5) && launch_integral(s, iw, ih, nn, rowp, /*sq=*/true)) {
+      GS_LAUNCH(k_tm_s2_corners, dim3((rw + 255) / 256, rh, nn), dim3(256), 0, st, (const unsigned *)rowp, iw, ih, tw, th, rw, rh, s2);
+    } else {
+      GS_LAUNCH(k_tm_rowprefix, dim3((ih + 3) / 4, 1, nn), dim3(64, 4), 0, st, s, iw, ih, rowp);
+      GS_LAUNCH(k_tm_colsq, dim3((rw + 63) / 64, (rh + kTmRun - 1) / kTmRun, nn), dim3(64), 0, st, (const unsigned *)rowp, iw, ih, tw, th,
+                rw, rh, s2);
+    }
+#ifndef GS_EMU
+    /* more than the default 64 KB of dynamic LDS: a per-DEVICE attribute of the function (ADVICE r03: a thread that moved to
+     * another device with gsh_set_device kept a thread-local "done" flag and the launch failed there) */
+    static std::atomic<unsigned long long> lds_raised{0};
+    const unsigned long long dev_bit = 1ull << ((unsigned)ctx().device & 63u);
+    if (ctx().device >= 64 || !(lds_raised.load(std::memory_order_acquire) & dev_bit)) {
+#define GS_TM_FNS(S) (const void *)k_match_template_mfma<S, 2>, (const void *)k_match_template_mfma<S, 3>, (const void *)k_match_template_mfma<S, 4>, \
+                     (const void *)k_match_template_mfma<S, 5>, (const void *)k_match_template_mfma<S, 6>, (const void *)k_match_template_mfma<S, 7>, \
+                     (const void *)k_match_template_mfma<S, 8>, (const void *)k_match_template_mfma<S, 9>
+      const void *fns[] = {GS_TM_FNS(1), GS_TM_FNS(4),
+                           (const void *)k_match_template_mfma<1, 2, true>, (const void *)k_match_template_mfma<1, 3, true>, (const void *)k_match_template_mfma<1, 4, true>,
+                           (const void *)k_match_template_mfma<1, 5, true>, (const void *)k_match_template_mfma<1, 6, true>, (const void *)k_match_template_mfma<1, 7, true>,
+                           (const void *)k_match_template_mfma<1, 8, true>, (const void *)k_match_template_mfma<1, 9, true>};
+#undef GS_TM_FNS
+      for (const void *fn : fns) GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      lds_raised.fetch_or(dev_bit, std::memory_order_release);
+    }
+#endif
+    TmArgs ta{s, iw, ih, (const uint8_t *)tpad, (const unsigned *)tsqp, tw, th, s2, d, rw, rh, nkc, istride, tstride,
+              ntmpl > 1 ? (unsigned)tpb : 0u, ntmpl > 1 ? 1u : 0u, keys};
+    /* one instantiation per number of K steps (k_tmatch.h): nkc = 2 .. 9 for templates 16 .. 257 wide */
+    const dim3 gs4((rw + 63) / 64, (rh + 31) / 32, nn), gs1((rw + 127) / 128, (rh + 63) / 64, nn);
+    GS_ASSERT(nkc >= 2 && nkc <= 9);
+    switch (nkc * 4 + (tm_split ? 1u : tm_band ? 2u : 0u)) {
+#define GS_TM_CASE(K)                                                                                   \
+  case K * 4: GS_LAUNCH((k_match_template_mfma<1, K>), gs1, dim3(256), tm_lds, st, ta); break;          \
+  case K * 4 + 1: GS_LAUNCH((k_match_template_mfma<4, K>), gs4, dim3(256), tm_lds, st, ta); break;      \
+  case K * 4 + 2: GS_LAUNCH((k_match_template_mfma<1, K, true>), gs1, dim3(256), tm_lds, st, ta); break;
+      GS_TM_CASE(2) GS_TM_CASE(3) GS_TM_CASE(4) GS_TM_CASE(5) GS_TM_CASE(6) GS_TM_CASE(7) GS_TM_CASE(8) GS_TM_CASE(9)
+#undef GS_TM_CASE
+    }
+    return;
+  }
+  GS_ASSERT(d != nullptr); /* the other routes locate through a map (tm_batch) */
+  const dim3 g((rw + 63) / 64, (rh + 3) / 4, nn);
+  const unsigned tstep = ntmpl > 1 ? (unsigned)tb : 0u;
+  if (route == TM_DOT) {
+    unsigned long long *tsq = (unsigned long long *)ctx().scratch(SL_PFX, (size_t)ntmpl * 8);
+    GS_LAUNCH(k_sum_squares, dim3(ntmpl), dim3(256), 0, st, t, (unsigned long long)tb, tsq);
+    const size_t twp = ((size_t)tw + 3) & ~(size_t)3;
+    const size_t lds = std::min<size_t>(twp * th, (kTmplTile / twp) * twp);
+    /* four results per thread when image rows start 4-byte aligned (see k_match_template4) */
+    if (iw % 4 == 0 && ((uintptr_t)s & 3) == 0 && ib < 0x7fffffffull)
+      GS_LAUNCH(k_match_template4, dim3((rw + 255) / 256, (rh + 3) / 4, nn), dim3(64, 4), lds, st, s, iw, ih, t, tw, th, tstep,
+                (const unsigned long long *)tsq, d, rw, rh);
+    else
+      GS_LAUNCH(k_match_template, g, dim3(64, 4), lds, st, s, iw, ih, t, tw, th, tstep, (const unsigned long long *)tsq, d, rw, rh);
+  } else {
+    GS_LAUNCH(k_match_template_px, g, dim3(64, 4), 0, st, s, iw, ih, t, tw, th, tstep, d, rw, rh);
+  }
+}
+/* best / score of n maps of rw x rh from their keys; maps == nullptr: the keys are there already */
+static void tm_argmax(const uint8_t *maps, unsigned rw, unsigned rh, unsigned n, unsigned long long *keys) {
+  const unsigned long long rb = (unsigned long long)rw * rh;
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const unsigned nn = std::min(kMaxZ, n - f0);
+    GS_LAUNCH(k_argmax_first, dim3((unsigned)((rb + 2047) / 2048), nn), dim3(256), 0, ctx().s(), maps + (size_t)rb * f0, rb,
+              (unsigned long long *)nullptr, keys + f0);
+  }
+}
+/* gsh_match_template_batch (result != nullptr) and gsh_locate_template_batch (best != nullptr) */
+static void tm_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
+                     uint8_t *result, struct gs_point *best, uint8_t *score) {
+  if (n == 0) return;
+  GS_ASSERT(img && iw > 0 && ih > 0 && tmpl && tw > 0 && th > 0 && (result || best));
+  GS_ASSERT(iw >= tw && ih >= th);
+  GS_ASSERT(ntmpl == 1 || ntmpl == n);
+  const unsigned rw = iw - tw + 1, rh = ih - th + 1;
+  const size_t ib = (size_t)iw * ih, tb = (size_t)tw * th, rb = (size_t)rw * rh;
+  const TmRoute route = tm_route(iw, ih, tw, th);
+  const unsigned chunk = tm_chunk_frames(route, iw, ih, rw, rh, n, result == nullptr);
+  hipStream_t st = ctx().s();
+  unsigned long long *keys = nullptr;
+  if (!result) {
+    keys = (unsigned long long *)ctx().scratch(SL_BEST, (size_t)n * 8);
+    GS_HIP(hipMemsetAsync(keys, 0, (size_t)n * 8, st));
+  }
+  for (unsigned f0 = 0; f0 < n; f0 += chunk) {
+    const unsigned nn = std::min(chunk, n - f0);
+    const uint8_t *s = img + ib * f0, *t = ntmpl > 1 ? tmpl + tb * f0 : tmpl;
+    const unsigned nt = ntmpl > 1 ? nn : 1u;
+    if (result) tm_launch(s, iw, ih, nn, t, tw, th, nt, result + rb * f0, nullptr);
+    else if (route == TM_MFMA) tm_launch(s, iw, ih, nn, t, tw, th, nt, nullptr, keys + f0);
+    else { /* a chunk's maps in scratch, then the batched argmax */
+      uint8_t *maps = (uint8_t *)ctx().scratch(SL_OUT, (size_t)nn * rb);
+      tm_launch(s, iw, ih, nn, t, tw, th, nt, maps, nullptr);
+      tm_argmax(maps, rw, rh, nn, keys + f0);
+    }
+  }
+  if (!result) GS_LAUNCH(k_best_from_keys, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, rw, (unsigned *)best, score);
+}
+
 }  // namespace gsi
 
 extern "C" {
@@ -868,6 +1043,30 @@ void gsh_crop_resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t
   launch_resize(dst, dw, dh, src, sw, sh, n, (const unsigned *)rois_dev, frame_of_dev, npatches, nearest != 0);
 }
 
+/* ---- template matching over a batch (ref :705, :726; docs/design/stencils.md) ------------------------------------------ */
+void gsh_match_template_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th,
+                              unsigned ntmpl, uint8_t *result) {
+  if (n == 0) return;
+  GS_ASSERT(result != NULL);
+  tm_batch(img, iw, ih, n, tmpl, tw, th, ntmpl, result, nullptr, nullptr);
+}
+void gsh_find_best_match_batch(const uint8_t *result, unsigned rw, unsigned rh, unsigned n, struct gs_point *best, uint8_t *score) {
+  if (n == 0) return;
+  GS_ASSERT(result && rw > 0 && rh > 0 && best);
+  hipStream_t st = ctx().s();
+  unsigned long long *keys = (unsigned long long *)ctx().scratch(SL_BEST, (size_t)n * 8);
+  GS_HIP(hipMemsetAsync(keys, 0, (size_t)n * 8, st));
+  tm_argmax(result, rw, rh, n, keys);
+  GS_LAUNCH(k_best_from_keys, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, rw, (unsigned *)best, score);
+}
+void gsh_locate_template_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th,
+                               unsigned ntmpl, struct gs_point *best, uint8_t *score) {
+  if (n == 0) return;
+  GS_ASSERT(best != NULL);
+  tm_batch(img, iw, ih, n, tmpl, tw, th, ntmpl, nullptr, best, score);
+}
+
+
 /* ---------------------------------------------------------------- synthetic frames, checksums */
 void gsh_synth_batch(uint8_t *dst, unsigned w, unsigned h, unsigned n, uint32_t seed0) {
   GS_ASSERT(dst && w > 0 && h > 0);
@@ -1050,86 +1249,7 @@ void gs_match_template(struct gs_image img, struct gs_image tmpl, struct gs_imag
   const uint8_t *t = (const uint8_t *)stage_in(tmpl.data, tb, SL_AUX);
   const bool dhost = !is_dev(result.data);
   uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, rb) : result.data;
-  const dim3 g((result.w + 63) / 64, (result.h + 3) / 4);
-  /* templates of 512 .. 32768 taps, 16 .. 257 wide, whose block fits the LDS: the cross term on the matrix cores (k_tmatch.h;
-   * smaller ones are as fast on the dot-product kernels: 1280x720, 16 x 16: 39 vs 47 us).
-   * gsh_tune key 20 = 1: the VALU dot-product kernels below; 2 / 3: always 64 x 128 tiles / always 32 x 64 tiles with split rows. */
-  /* few 64 x 128 tiles (video-sized images): 32 x 64 tiles, the template rows split over the block's four waves */
-  const bool tm_split = g_tune[20] == 3 || (g_tune[20] != 2 && g_tune[20] != 8 && (unsigned long long)((result.w + 127) / 128) * ((result.h + 63) / 64) < 512); /* key 20 = 8: 64 x 128 tiles, banded, whatever the size */
-  const unsigned nkc = (tmpl.w + 31 + 31) / 32, istride = (tm_split ? 32 : 96) + 32 * nkc + 16, tstride = 32 * nkc + 48;
-  /* SPLIT = 1 takes templates taller than a band kTmBand rows at a time (k_tmatch.h BAND: 33 KB of LDS per block instead of 79 at
-   * 128 x 128, four blocks per CU); key 20 = 2: the whole template resident, as in round 3 */
-  const bool tm_band = !tm_split && g_tune[20] != 2 && tmpl.h > kTmBand;
-  const unsigned tm_rows = tm_band ? kTmBand : tmpl.h;
-  const size_t tm_lds = std::max<size_t>((size_t)((tm_split ? 31 : 63) + tm_rows) * istride + (size_t)tm_rows * tstride + 16,
-                                         tm_split ? 32768 : 0);
-  if (g_tune[20] != 1 && tmpl.w >= 16 && nkc <= 9 && tmpl.h >= 4 && (tb >= 512 || g_tune[20] == 2 || g_tune[20] == 3 || g_tune[20] == 8) && tb <= 32768 && tm_lds <= 150 * 1024 &&
-      ib < 0x7fffffffull) {
-    hipStream_t st = ctx().s();
-    unsigned *rowp = (unsigned *)ctx().scratch(SL_II, (size_t)img.h * (img.w + 1) * 4);
-    unsigned *s2 = (unsigned *)ctx().scratch(SL_PAD, rb * 4);
-    uint8_t *tpad = (uint8_t *)ctx().scratch(SL_PRE, (size_t)tmpl.h * tstride + 16);
-    unsigned *tsqp = (unsigned *)(tpad + (((size_t)tmpl.h * tstride + 3) & ~(size_t)3)); /* tstride is a multiple of 16 */
-    GS_LAUNCH(k_tm_prep, dim3(1), dim3(1024), 0, st, t, tmpl.w, tmpl.h, tstride, tpad, tsqp);
-    /* window sums of (I - 128)^2: four corners of the banded integral table of squares (round 4) for frames of 4 Mpx and
-     * more -- 4K, 128 x 128: 0.269 -> 0.249 ms, 64 x 64: 0.135 -> 0.125; on a 720p frame the four short launches are 6-10 us
-     * SLOWER than the two passes of round 3 (row prefix + sliding columns), which stay for small frames, for key 20 = 4 and
-     * for geometries the banded integral does not take (key 20 = 5: the table route whatever the size);
-     * profiles/r04v_match_template_integral_squares.log */
-    if (g_tune[20] != 4 && (ib >= (4u << 20) || g_tune[20] == 5) && launch_integral(s, img.w, img.h, 1, rowp, /*sq=*/true)) {
-      GS_LAUNCH(k_tm_s2_corners, dim3((result.w + 255) / 256, result.h), dim3(256), 0, st, (const unsigned *)rowp, img.w, tmpl.w, tmpl.h,
-                result.w, result.h, s2);
-    } else {
-      GS_LAUNCH(k_tm_rowprefix, dim3((img.h + 3) / 4), dim3(64, 4), 0, st, s, img.w, img.h, rowp);
-      GS_LAUNCH(k_tm_colsq, dim3((result.w + 63) / 64, (result.h + kTmRun - 1) / kTmRun), dim3(64), 0, st, (const unsigned *)rowp,
-                img.w, tmpl.w, tmpl.h, result.w, result.h, s2);
-    }
-#ifndef GS_EMU
-    /* more than the default 64 KB of dynamic LDS: a per-DEVICE attribute of the function (ADVICE r03: a thread that moved to
-     * another device with gsh_set_device kept a thread-local "done" flag and the launch failed there) */
-    static std::atomic<unsigned long long> lds_raised{0};
-    const unsigned long long dev_bit = 1ull << ((unsigned)ctx().device & 63u);
-    if (ctx().device >= 64 || !(lds_raised.load(std::memory_order_acquire) & dev_bit)) {
-#define GS_TM_FNS(S) (const void *)k_match_template_mfma<S, 2>, (const void *)k_match_template_mfma<S, 3>, (const void *)k_match_template_mfma<S, 4>, \
-                     (const void *)k_match_template_mfma<S, 5>, (const void *)k_match_template_mfma<S, 6>, (const void *)k_match_template_mfma<S, 7>, \
-                     (const void *)k_match_template_mfma<S, 8>, (const void *)k_match_template_mfma<S, 9>
-      const void *fns[] = {GS_TM_FNS(1), GS_TM_FNS(4),
-                           (const void *)k_match_template_mfma<1, 2, true>, (const void *)k_match_template_mfma<1, 3, true>, (const void *)k_match_template_mfma<1, 4, true>,
-                           (const void *)k_match_template_mfma<1, 5, true>, (const void *)k_match_template_mfma<1, 6, true>, (const void *)k_match_template_mfma<1, 7, true>,
-                           (const void *)k_match_template_mfma<1, 8, true>, (const void *)k_match_template_mfma<1, 9, true>};
-#undef GS_TM_FNS
-      for (const void *fn : fns) GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      lds_raised.fetch_or(dev_bit, std::memory_order_release);
-    }
-#endif
-    TmArgs ta{s, img.w, img.h, (const uint8_t *)tpad, (const unsigned *)tsqp, tmpl.w, tmpl.h, s2, d, result.w, result.h, nkc, istride, tstride};
-    /* one instantiation per number of K steps (k_tmatch.h): nkc = 2 .. 9 for templates 16 .. 257 wide */
-    const dim3 gs4((result.w + 63) / 64, (result.h + 31) / 32), gs1((result.w + 127) / 128, (result.h + 63) / 64);
-    GS_ASSERT(nkc >= 2 && nkc <= 9);
-    switch (nkc * 4 + (tm_split ? 1u : tm_band ? 2u : 0u)) {
-#define GS_TM_CASE(K)                                                                                   \
-  case K * 4: GS_LAUNCH((k_match_template_mfma<1, K>), gs1, dim3(256), tm_lds, st, ta); break;          \
-  case K * 4 + 1: GS_LAUNCH((k_match_template_mfma<4, K>), gs4, dim3(256), tm_lds, st, ta); break;      \
-  case K * 4 + 2: GS_LAUNCH((k_match_template_mfma<1, K, true>), gs1, dim3(256), tm_lds, st, ta); break;
-      GS_TM_CASE(2) GS_TM_CASE(3) GS_TM_CASE(4) GS_TM_CASE(5) GS_TM_CASE(6) GS_TM_CASE(7) GS_TM_CASE(8) GS_TM_CASE(9)
-#undef GS_TM_CASE
-    }
-  } else if (tmpl.w <= kTmplTile - 3) {
-    unsigned long long *tsq = (unsigned long long *)ctx().scratch(SL_PFX, 8);
-    GS_LAUNCH(k_sum_squares, dim3(1), dim3(256), 0, ctx().s(), t, (unsigned long long)tb, tsq);
-    const size_t twp = ((size_t)tmpl.w + 3) & ~(size_t)3;
-    const size_t lds = std::min<size_t>(twp * tmpl.h, (kTmplTile / twp) * twp);
-    /* four results per thread when image rows start 4-byte aligned (see k_match_template4) */
-    if (img.w % 4 == 0 && ((uintptr_t)s & 3) == 0 && (size_t)img.w * img.h < 0x7fffffffull)
-      GS_LAUNCH(k_match_template4, dim3((result.w + 255) / 256, (result.h + 3) / 4), dim3(64, 4), lds, ctx().s(),
-                s, img.w, img.h, t, tmpl.w, tmpl.h, (const unsigned long long *)tsq, d, result.w, result.h);
-    else
-      GS_LAUNCH(k_match_template, g, dim3(64, 4), lds, ctx().s(), s, img.w, img.h, t, tmpl.w, tmpl.h,
-                (const unsigned long long *)tsq, d, result.w, result.h);
-  } else {
-    GS_LAUNCH(k_match_template_px, g, dim3(64, 4), 0, ctx().s(), s, img.w, img.h, t, tmpl.w, tmpl.h, d,
-              result.w, result.h);
-  }
+  tm_launch(s, img.w, img.h, 1, t, tmpl.w, tmpl.h, 1, d, nullptr); /* the batch launcher with one frame: route and tile form as ever */
   if (dhost) GS_HIP(hipMemcpyAsync(result.data, d, rb, hipMemcpyDeviceToHost, ctx().s()));
   finish(dhost);
 }
@@ -1139,7 +1259,7 @@ struct gs_point gs_find_best_match(struct gs_image result) { /* ref :726 */
   const uint8_t *s = (const uint8_t *)stage_in(result.data, (size_t)n, SL_IN);
   const unsigned blocks = (unsigned)((n + 2047) / 2048);
   unsigned long long *part = (unsigned long long *)ctx().scratch(SL_PFX, (size_t)blocks * 8);
-  GS_LAUNCH(k_argmax_first, dim3(blocks), dim3(256), 0, ctx().s(), s, n, part);
+  GS_LAUNCH(k_argmax_first, dim3(blocks), dim3(256), 0, ctx().s(), s, n, part, (unsigned long long *)nullptr);
   std::vector<unsigned long long> hp(blocks);
   GS_HIP(hipMemcpyAsync(hp.data(), part, (size_t)blocks * 8, hipMemcpyDeviceToHost, ctx().s()));
   ctx().sync();

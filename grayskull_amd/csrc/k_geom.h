@@ -14,10 +14,24 @@ GS_DEV unsigned geom_px(const uint8_t *img, unsigned w, unsigned h, unsigned x, 
   return (x < w && y < h) ? img[(size_t)y * w + x] : 0u;
 }
 
-/* sum of squares of n bytes into *out (one block of 256; the template's constant term) */
+/* the maximum of a 64-bit key over the wave, in every lane (xor butterfly over the two halves) */
+GS_DEV unsigned long long wave_max_u64(unsigned long long best) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t lo = shfl((uint32_t)best, (int)(lane_id() ^ (unsigned)d));
+    const uint32_t hi = shfl((uint32_t)(best >> 32), (int)(lane_id() ^ (unsigned)d));
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    best = o > best ? o : best;
+  }
+  return best;
+}
+
+/* sum of squares of n bytes into *out (one block of 256; the template's constant term); block b of the grid takes the b-th
+ * run of n bytes into out[b] (gsh_match_template_batch with one template per frame) */
 __global__ __launch_bounds__(256) void k_sum_squares(const uint8_t *v, unsigned long long n,
                                                      unsigned long long *out) {
   __shared__ unsigned long long part[4];
+  v += (size_t)blockIdx.x * n, out += blockIdx.x;
   unsigned long long acc = 0;
   for (unsigned long long i = threadIdx.x; i < n; i += 256u) acc += (unsigned long long)v[i] * v[i];
   unsigned lo = (unsigned)acc, hi = (unsigned)(acc >> 32); /* per-thread sums fit far below 2^63 */
@@ -40,12 +54,16 @@ __global__ __launch_bounds__(256) void k_sum_squares(const uint8_t *v, unsigned 
  * of a row go byte by byte.  Row sums (<= tw * 65025 < 2^32 for tw <= 16384) are added to 64-bit
  * totals after every template row.  Requires tw <= kTmplTile - 3 (wider: k_match_template_px). */
 constexpr unsigned kTmplTile = 16384;
+/* The three map kernels take the frame from blockIdx.z: frame f's image lies iw * ih bytes, its result rw * rh bytes behind
+ * frame f - 1's; tstep = 0: one template (and one tmpl_sq) for every frame, tstep = tw * th: template f for frame f. */
 __global__ __launch_bounds__(256) void k_match_template(const uint8_t *img, unsigned iw, unsigned ih,
-                                                        const uint8_t *tmpl, unsigned tw, unsigned th,
+                                                        const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstep,
                                                         const unsigned long long *tmpl_sq,
                                                         uint8_t *result, unsigned rw, unsigned rh) {
   GS_DYN_LDS(smem);
   uint8_t *lt = (uint8_t *)smem;
+  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rw * rh;
+  tmpl += (size_t)blockIdx.z * tstep, tmpl_sq += tstep ? blockIdx.z : 0u;
   const unsigned tid = threadIdx.y * 64u + threadIdx.x;
   const unsigned rx = blockIdx.x * 64u + threadIdx.x, ry = blockIdx.y * 4u + threadIdx.y;
   const bool live = rx < rw && ry < rh;
@@ -93,11 +111,13 @@ __global__ __launch_bounds__(256) void k_match_template(const uint8_t *img, unsi
  * needs 4 overlapping unaligned loads for the same work).  grid (ceil(rw/4/64), ceil(rh/4)). */
 
 __global__ __launch_bounds__(256) void k_match_template4(const uint8_t *img, unsigned iw, unsigned ih,
-                                                         const uint8_t *tmpl, unsigned tw, unsigned th,
+                                                         const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstep,
                                                          const unsigned long long *tmpl_sq,
                                                          uint8_t *result, unsigned rw, unsigned rh) {
   GS_DYN_LDS(smem);
   uint8_t *lt = (uint8_t *)smem;
+  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rw * rh;
+  tmpl += (size_t)blockIdx.z * tstep, tmpl_sq += tstep ? blockIdx.z : 0u;
   const unsigned tid = threadIdx.y * 64u + threadIdx.x;
   const unsigned rx0 = (blockIdx.x * 64u + threadIdx.x) * 4u, ry = blockIdx.y * 4u + threadIdx.y;
   const bool live = rx0 < rw && ry < rh;
@@ -157,10 +177,11 @@ __global__ __launch_bounds__(256) void k_match_template4(const uint8_t *img, uns
 
 /* any template width: one subtract-multiply-add per tap, template read from global memory */
 __global__ __launch_bounds__(256) void k_match_template_px(const uint8_t *img, unsigned iw, unsigned ih,
-                                                           const uint8_t *tmpl, unsigned tw, unsigned th,
+                                                           const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstep,
                                                            uint8_t *result, unsigned rw, unsigned rh) {
   const unsigned rx = blockIdx.x * 64u + threadIdx.x, ry = blockIdx.y * 4u + threadIdx.y;
   if (rx >= rw || ry >= rh) return;
+  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rw * rh, tmpl += (size_t)blockIdx.z * tstep;
   unsigned long long sum = 0;
   for (unsigned ty = 0; ty < th; ty++)
     for (unsigned tx = 0; tx < tw; tx++) {
@@ -173,12 +194,16 @@ __global__ __launch_bounds__(256) void k_match_template_px(const uint8_t *img, u
 }
 
 /* gs_find_best_match: key = value << 32 | ~index: the maximum key is the largest value at the
- * LOWEST raster index (the reference's strict '>' keeps the first maximum).  grid ceil(n/2048)
- * blocks of 256, 8 items per thread; out[blockIdx.x] = block maximum; the host (or a second
- * launch over `out`) finishes.  A zero maximum means (0,0) like the reference's initial state. */
+ * LOWEST raster index (the reference's strict '>' keeps the first maximum).  grid (ceil(n/2048), frames)
+ * blocks of 256, 8 items per thread; frame blockIdx.y lies n bytes behind the one before it.
+ * keys == NULL (gs_find_best_match, one frame): out[blockIdx.x] = block maximum and the host finishes.
+ * keys != NULL (gsh_find_best_match_batch): a block whose maximum has a non-zero value issues one 64-bit atomicMax on
+ * keys[blockIdx.y], zeroed before the launch -- the maximum of the keys does not depend on the order in which blocks
+ * arrive --, and k_best_from_keys finishes.  A zero maximum means (0,0) like the reference's initial state. */
 __global__ __launch_bounds__(256) void k_argmax_first(const uint8_t *v, unsigned long long n,
-                                                      unsigned long long *out) {
+                                                      unsigned long long *out, unsigned long long *keys) {
   __shared__ unsigned long long part[4];
+  v += (size_t)blockIdx.y * n;
   unsigned long long best = 0;
   for (unsigned k = 0; k < 8; k++) {
     const unsigned long long i = ((unsigned long long)blockIdx.x * 8u + k) * 256u + threadIdx.x;
@@ -187,19 +212,26 @@ __global__ __launch_bounds__(256) void k_argmax_first(const uint8_t *v, unsigned
       best = key > best ? key : best;
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = shfl((uint32_t)best, (int)(lane_id() ^ (unsigned)d));
-    const uint32_t hi = shfl((uint32_t)(best >> 32), (int)(lane_id() ^ (unsigned)d));
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    best = o > best ? o : best;
-  }
+  best = wave_max_u64(best);
   if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = best;
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int q = 1; q < 4; q++) best = part[q] > best ? part[q] : best;
-    out[blockIdx.x] = best;
+    if (!keys) out[blockIdx.x] = best;
+    else if (best >> 32) atomicMax(keys + blockIdx.y, best);
   }
+}
+
+/* n keys (value << 32 | ~(y * rw + x), 0 in the high half: no non-zero value seen) -> n points {x, y} and n values;
+ * best: two unsigned per frame (struct gs_point), score may be NULL.  grid ceil(n / 256), block 256 */
+__global__ __launch_bounds__(256) void k_best_from_keys(const unsigned long long *keys, unsigned n, unsigned rw, unsigned *best,
+                                                        uint8_t *score) {
+  const unsigned f = blockIdx.x * 256u + threadIdx.x;
+  if (f >= n) return;
+  const unsigned long long key = keys[f];
+  const unsigned v = (unsigned)(key >> 32), idx = 0xffffffffu - (unsigned)key;
+  best[2u * f] = v ? idx % rw : 0u, best[2u * f + 1u] = v ? idx / rw : 0u;
+  if (score) score[f] = (uint8_t)v;
 }
 
 }  // namespace gs

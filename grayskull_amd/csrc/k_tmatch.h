@@ -21,8 +21,14 @@
 #ifndef GS_K_TMATCH_H
 #define GS_K_TMATCH_H
 #include "prims.h"
+#include "k_geom.h" /* wave_max_u64, the key of k_argmax_first */
 
 namespace gs {
+
+/* A FRAME AXIS (gsh_match_template_batch, gsh_locate_template_batch): every kernel here but k_tm_prep takes the frame from
+ * blockIdx.z -- frame f's image lies iw * ih bytes, its prefix table pstride, its s2 plane and its result rw * rh entries
+ * behind frame f - 1's -- and k_tm_prep prepares template blockIdx.x.  The launcher hands a launch as many frames as its
+ * scratch budget allows (gs_stencil.cpp), so a clip of video-sized frames fills the chip with whole 64 x 128 tiles. */
 
 struct TmArgs {
   const uint8_t *img;
@@ -36,13 +42,21 @@ struct TmArgs {
   unsigned nkc;     /* K steps of 32: ceil((tw + 31) / 32) */
   unsigned istride; /* LDS image row: 96 + 32 nkc bytes + 16 (an odd number of 16-byte slots: conflict-free b128 reads) */
   unsigned tstride; /* template row: 32 zeros, the row, zeros up to 32 nkc + 48 (a multiple of 16) */
+  /* frame blockIdx.z: img, s2 and result move on by one frame, tpad by tstep bytes and tsq by sqstep entries (0: one
+   * template for every frame; th * tstride and 1: one per frame) */
+  unsigned tstep, sqstep;
+  /* result == nullptr: the locate epilogue -- no score byte is stored; keys[blockIdx.z] (zeroed before the launch) receives
+   * the maximum of score << 32 | ~(ry * rw + rx) over the frame, one 64-bit atomicMax per wave that saw a non-zero score */
+  unsigned long long *keys;
 };
 
 /* the template as the MFMA kernel wants it: th rows of tstride bytes (32 zeros, T ^ 0x80, zeros), and sum (T - 128)^2.
- * One block of 1024 threads (a template has at most 32768 taps). */
+ * One block of 1024 threads per template (a template has at most 32768 taps): block b reads template b (tw * th bytes each)
+ * and writes padded template b (th * tstride bytes each) and tsq[b]. */
 __global__ __launch_bounds__(1024) void k_tm_prep(const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstride, uint8_t *tpad,
                                                    unsigned *tsq) {
   __shared__ unsigned part[16];
+  tmpl += (size_t)blockIdx.x * tw * th, tpad += (size_t)blockIdx.x * th * tstride, tsq += blockIdx.x;
   const unsigned tid = threadIdx.x, tdw = tstride / 4u, ntd = th * tdw;
   unsigned t2 = 0;
   for (unsigned i = tid; i < ntd; i += 1024u) {
@@ -68,10 +82,11 @@ __global__ __launch_bounds__(1024) void k_tm_prep(const uint8_t *tmpl, unsigned 
 }
 
 /* P[r][x] = sum_{i < x} (I[r][i] - 128)^2 for x = 0 .. iw (iw + 1 entries per row): one wave per row, 16 pixels per lane
- * and pass, a wave scan per pass.  grid (ceil(ih / 4)), block (64, 4) */
+ * and pass, a wave scan per pass.  grid (ceil(ih / 4), 1, frames), block (64, 4) */
 __global__ __launch_bounds__(256) void k_tm_rowprefix(const uint8_t *img, unsigned iw, unsigned ih, unsigned *P) {
   const unsigned r = blockIdx.x * 4u + threadIdx.y, lane = threadIdx.x;
   if (r >= ih) return; /* whole wave */
+  img += (size_t)blockIdx.z * iw * ih, P += (size_t)blockIdx.z * ih * (iw + 1u);
   const uint8_t *row = img + (size_t)r * iw;
   unsigned *o = P + (size_t)r * (iw + 1u);
   unsigned carry = 0;
@@ -114,13 +129,15 @@ __global__ __launch_bounds__(256) void k_tm_rowprefix(const uint8_t *img, unsign
   }
 }
 /* s2[y][x] = sum_{j < th} (P[y + j][x + tw] - P[y + j][x]); a thread slides down kTmRun result rows of one column, the rows
- * that enter and leave requested 16 steps at a time.  grid (ceil(rw / 64), ceil(rh / kTmRun)), block 64 */
+ * that enter and leave requested 16 steps at a time.  grid (ceil(rw / 64), ceil(rh / kTmRun), frames), block 64;
+ * ih: the rows of a frame's table (the frames' tables lie ih * (iw + 1) entries apart) */
 constexpr unsigned kTmRun = 64;
-__global__ __launch_bounds__(64) void k_tm_colsq(const unsigned *P, unsigned iw, unsigned tw, unsigned th, unsigned rw, unsigned rh,
-                                                 unsigned *s2) {
+__global__ __launch_bounds__(64) void k_tm_colsq(const unsigned *P, unsigned iw, unsigned ih, unsigned tw, unsigned th, unsigned rw,
+                                                 unsigned rh, unsigned *s2) {
   const unsigned x = blockIdx.x * 64u + threadIdx.x, y0 = blockIdx.y * kTmRun;
   if (x >= rw) return;
   const size_t ps = (size_t)iw + 1u;
+  P += (size_t)blockIdx.z * ih * ps, s2 += (size_t)blockIdx.z * rw * rh;
   const unsigned last = rh - 1u + th - 1u; /* last image row a window touches */
   auto h = [&](unsigned r) { /* rows past the image only feed results that are not stored */
     const unsigned rr = r <= last ? r : last;
@@ -144,11 +161,13 @@ __global__ __launch_bounds__(64) void k_tm_colsq(const unsigned *P, unsigned iw,
 
 /* s2 from the integral table Q of (I - 128)^2 (k_integral.h, SQ; round 4): four corners per result, modulo 2^32 like the
  * table -- three short launches for the table and this one instead of the row-prefix + sliding-column passes above, which
- * move 140 MB through a u32 prefix table for a 4K frame (75 us; this route: see DESIGN.md 3).  grid (ceil(rw / 256), rh), block 256 */
-__global__ __launch_bounds__(256) void k_tm_s2_corners(const unsigned *Q, unsigned iw, unsigned tw, unsigned th, unsigned rw, unsigned rh,
-                                                      unsigned *s2) {
+ * move 140 MB through a u32 prefix table for a 4K frame (75 us; this route: see DESIGN.md 3).  grid (ceil(rw / 256), rh, frames),
+ * block 256; the frames' tables lie iw * ih entries apart, as launch_integral leaves them */
+__global__ __launch_bounds__(256) void k_tm_s2_corners(const unsigned *Q, unsigned iw, unsigned ih, unsigned tw, unsigned th, unsigned rw,
+                                                      unsigned rh, unsigned *s2) {
   const unsigned x = blockIdx.x * 256u + threadIdx.x, y = blockIdx.y;
   if (x >= rw) return;
+  Q += (size_t)blockIdx.z * iw * ih, s2 += (size_t)blockIdx.z * rw * rh;
   const unsigned *lo = Q + (size_t)(y + th - 1u) * iw, *hi = y ? Q + (size_t)(y - 1u) * iw : nullptr;
   unsigned s = lo[x + tw - 1u];
   if (x) s -= lo[x - 1u];
@@ -176,12 +195,19 @@ __global__ __launch_bounds__(256) void k_tm_s2_corners(const unsigned *Q, unsign
  * tw = 128 instead of 79 and FOUR blocks (16 waves, four per SIMD) fit a CU instead of two: the kernel is paced by LDS
  * latency under the occupancy its footprint allows.  The rows shared by consecutive bands are staged again
  * (they come from the L2). */
+/* The frame axis and the locate epilogue are run-time arguments (TmArgs), wave-uniform, so the batch entries add no
+ * instantiation: SPLIT x NK x BAND stays at 24 kernels (docs/design/stencils.md has their registers before and after). */
 constexpr unsigned kTmBand = 32;
 template <int SPLIT, unsigned NK = 9, bool BAND = false>
 __global__ __launch_bounds__(256) void k_match_template_mfma(TmArgs a) {
   static_assert(SPLIT == 1 || !BAND, "the split form keeps the whole template resident");
   GS_DYN_LDS(smem);
   const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  { /* this block's frame (scalar arithmetic on the kernel's arguments) */
+    const size_t f = blockIdx.z;
+    a.img += f * a.iw * a.ih, a.s2 += f * a.rw * a.rh, a.tpad += f * a.tstep, a.tsq += f * a.sqstep;
+    if (a.result) a.result += f * a.rw * a.rh;
+  }
   constexpr unsigned TR = SPLIT == 1 ? 64u : 32u, TC = SPLIT == 1 ? 128u : 64u;
   const unsigned bx0 = blockIdx.x * TC, by0 = blockIdx.y * TR;
   const unsigned jband = BAND ? kTmBand : a.th; /* template rows resident at a time */
@@ -313,6 +339,7 @@ __global__ __launch_bounds__(256) void k_match_template_mfma(TmArgs a) {
     const unsigned y = by0 + wy + (unsigned)((r & 3) + 8 * (r >> 2)) + 4u * g;
     return (x < a.rw && y < a.rh) ? a.s2[(size_t)y * a.rw + x] : 0u;
   };
+  unsigned long long best = 0; /* the locate epilogue's key: the largest score at the lowest raster index of this lane's results */
   auto finish = [&](int c, int r, int d, unsigned s2v) {
     const unsigned x = bx0 + wx + 32u * (unsigned)c + m;
     const unsigned y = by0 + wy + (unsigned)((r & 3) + 8 * (r >> 2)) + 4u * g;
@@ -323,7 +350,11 @@ __global__ __launch_bounds__(256) void k_match_template_mfma(TmArgs a) {
       if (rem < 0) q--;
       else if ((unsigned)rem >= dv) q++;
       const unsigned score = q < 255u ? q : 255u;
-      a.result[(size_t)y * a.rw + x] = (uint8_t)(255u - score);
+      if (a.result) a.result[(size_t)y * a.rw + x] = (uint8_t)(255u - score); /* wave-uniform */
+      else {
+        const unsigned long long key = ((unsigned long long)(255u - score) << 32) | (0xffffffffu - (y * a.rw + x));
+        best = key > best ? key : best;
+      }
     }
   };
   if constexpr (SPLIT == 1) {
@@ -354,6 +385,11 @@ __global__ __launch_bounds__(256) void k_match_template_mfma(TmArgs a) {
       for (unsigned w = 0; w < 4; w++) d += red[(w * 32u + v) * 64u + lane];
       finish((int)(v >> 4), (int)(v & 15u), d, sv[k]);
     }
+  }
+  if (!a.result) { /* wave-uniform; every lane of the wave is here.  The maximum over all waves of all blocks is the frame's
+                    * first maximum whatever order they arrive in; a wave that saw only zeros leaves the key word alone */
+    best = wave_max_u64(best);
+    if (lane == 0 && (best >> 32)) atomicMax(a.keys + blockIdx.z, best);
   }
 }
 

@@ -82,8 +82,10 @@ enum gsh_tune_key {
   GSH_TUNE_EXPERIMENT_22 = 22,    /* GS_EXPERIMENT builds only: gs_sobel without the reads that preserve columns 0 / w-1 */
   GSH_TUNE_EXPERIMENT_23 = 23,    /* GS_EXPERIMENT builds only: the strip-copy probe keeps the stencils' halo load */
   GSH_TUNE_RETIRED_24 = 24,       /* retired (realigning strip flavour never / always) */
-  GSH_TUNE_GEOM_FORM = 25         /* the resize kernels: 1 gather every tap from global memory (no LDS staging), 2 stage the source
+  GSH_TUNE_GEOM_FORM = 25,        /* the resize kernels: 1 gather every tap from global memory (no LDS staging), 2 stage the source
                                      rectangle wherever it fits the LDS, also beyond four source pixels per result pixel */
+  GSH_TUNE_TMATCH_CHUNK = 26      /* most frames per chunk of the template-matching batch entries (0 = by their scratch budget; test
+                                     hook: a chunk boundary with three small frames) */
 };
 void gsh_tune(int key, int value);
 /* measurement aid for bench.py: while on, gsh_edge_pipeline_batch brackets every launch of its
@@ -253,6 +255,30 @@ void gsh_resize_nn_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *
 void gsh_crop_resize_batch(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n,
                            const struct gs_rect *rois_dev, const unsigned *frame_of_dev /* NULL: patch p comes from frame p */,
                            unsigned npatches, int nearest);
+
+/* ---- template matching over a batch (ref :705, :726; docs/design/stencils.md "Template matching over a batch") -----
+ * All pointers device pointers, stream-ordered on the current stream, no host synchronisation and no read-back (the
+ * library's grow-only scratch synchronises once when it has to grow).  n == 0 returns before any check or launch.
+ * GS_ASSERT: non-NULL pointers, non-zero sizes, tw <= iw, th <= ih, ntmpl == 1 || ntmpl == n.
+ * Each frame takes the route gs_match_template takes for one frame of that size (matrix cores, dot products, wide
+ * templates); the matrix-core route chooses between its 64 x 128 and 32 x 64 tiles by the blocks of the whole launch.
+ * Scratch: the frames are worked through in chunks whose prefix tables and window sums (ih (iw + 1) 4 + rw rh 4 bytes
+ * per frame on the matrix-core route) stay within 128 MiB of context scratch whatever n is -- a single frame that needs
+ * more is a chunk of its own; GSH_TUNE_TMATCH_CHUNK caps the frames of a chunk. */
+/* n frames of iw x ih, frame f at img + f*iw*ih; ntmpl == 1: one template for all frames, ntmpl == n: template f at
+   tmpl + f*tw*th; result: n maps of rw x rh = (iw-tw+1) x (ih-th+1), each byte for byte the reference's gs_match_template */
+void gsh_match_template_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
+                              const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl, uint8_t *result);
+/* per frame the reference's gs_find_best_match (first maximum in raster order; an all-zero map gives {0,0});
+   score[f] = the map's value there (0 for an all-zero map); score may be NULL */
+void gsh_find_best_match_batch(const uint8_t *result, unsigned rw, unsigned rh, unsigned n,
+                               struct gs_point *best, uint8_t *score);
+/* == gsh_match_template_batch followed by gsh_find_best_match_batch, without a caller-visible result map: on the
+   matrix-core route no map is written at all (each wave sends its best score and place to the frame's key word with one
+   64-bit atomic maximum), the other routes keep a chunk's maps in scratch */
+void gsh_locate_template_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
+                               const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
+                               struct gs_point *best, uint8_t *score);
 
 /* ---- connected components, blob corners, perspective correction (ref :330, :404, :423) ----------
  * The reference's document-scanner chain (blur -> Otsu threshold -> gs_blobs -> largest blob ->
