@@ -379,8 +379,12 @@ inline int strip_mode(unsigned w, const void *src) {
 inline bool strip_ok16(unsigned w, unsigned h, const void *a, const void *b) {
   return w % 16 == 0 && (unsigned long long)w * h < 0x7fffffffull && al16(a) && al16(b);
 }
-/* frames per launch (grid.y / grid.z limit 65535); gsh_tune key 8 lowers it so that the splitting
- * logic of every launcher can be exercised with a handful of frames */
+/* frames per launch: the frame index rides in grid.y / grid.z, for which HIP documents CUDA's limit of 65535.  The
+ * runtime of ROCm 7.0 on gfx950 does not enforce it: some thirty launchers take grid.y from the ROWS of a frame, uncapped
+ * (only resize_plan caps it), and tests/test_gpu_shape_frontier.py runs each of them with grid.y = 65538 .. 65585 -- every
+ * launch runs and is bit-exact (docs/design/oracle_and_parity.md, "Shape frontier").  The split of the frames stays as it
+ * is, at the documented limit: nothing was measured that would pay for depending on what one runtime version tolerates.
+ * gsh_tune key 8 lowers it so that the splitting logic of every launcher can be exercised with a handful of frames */
 inline unsigned max_frames_per_launch() { return g_tune[8] > 0 ? (unsigned)g_tune[8] : 32768u; }
 #define kMaxZ (max_frames_per_launch())
 

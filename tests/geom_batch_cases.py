@@ -13,7 +13,9 @@ The launcher's rule (gs_stencil.cpp, resize_plan) is restated in `plan` so that 
 with more than four source pixels per result pixel (sw sh > 4 dw dh) the launch gets no LDS and every block gathers its
 taps from global memory.  Else a block of k_resize_tile covers 256 output columns and `band` output rows and stages at
 most E(256, sw, dw) x E(band, sh, dh) source bytes, E(c, s, d) = min(s, ceil(c s / d) + 3); the largest band of 16, 8, 4
-rows that needs at most 16 KiB is taken, else 4 rows if they need at most 48 KiB, else again no LDS."""
+rows that needs at most 16 KiB is taken, else 4 rows if they need at most 48 KiB, else again no LDS.  Whatever the form,
+at most 65535 bands: a taller result takes bands of ceil(dh / 65535) rows, rounded up to a multiple of 4, with the LDS
+size of the band it had (a block whose rectangle no longer fits gathers)."""
 import functools
 
 import numpy as np
@@ -21,6 +23,7 @@ import numpy as np
 FILL, GUARD = 0x5A, 0xA5
 PRE, POST = 64, 64
 LDS_SMALL, LDS_MAX = 16 * 1024, 48 * 1024
+MAX_BANDS = 65535
 
 
 def extent(c, s, d):
@@ -30,6 +33,13 @@ def extent(c, s, d):
 def plan(dw, dh, sw, sh, any_density=False):
     """(output rows per block, bytes of LDS) of gsh_resize_batch / gs_resize; 0 bytes = the gather form.  any_density:
     under gsh_tune(25, 2), which stages whatever the scale"""
+    band, lds = _plan_lds(dw, dh, sw, sh, any_density)
+    if (dh + band - 1) // band > MAX_BANDS:
+        band = ((dh + MAX_BANDS - 1) // MAX_BANDS + 3) & ~3
+    return band, lds
+
+
+def _plan_lds(dw, dh, sw, sh, any_density):
     if sw * sh > 4 * dw * dh and not any_density:
         return 16, 0
     pitch = (extent(min(dw, 256), sw, dw) + 3) & ~3

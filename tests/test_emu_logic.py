@@ -575,7 +575,8 @@ def fast_many_frames(g, oracle, n):
 
 
 def test_fast_batch_split_over_several_launches(emu, oracle):
-    """the frame index rides in grid.y / grid.z (limit 65535): every launcher splits big batches; gsh_tune
+    """the frame index rides in grid.y / grid.z (documented limit 65535; the ROCm 7.0 runtime takes more, as
+    tests/test_gpu_shape_frontier.py observes for row-derived grids): every launcher splits big batches; gsh_tune
     key 8 lowers the split size so that 40 frames already take three launches (the GPU suite runs 70,000)"""
     n = 40
     one, ko, smo = fast_many_frames(emu, oracle, n)

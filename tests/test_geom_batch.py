@@ -34,6 +34,11 @@ def test_the_rule_restated_for_the_tests():
     assert gc.plan(640, 360, 3840, 2160) == (16, 0) and gc.plan(300, 400, 612, 816) == (16, 0)
     assert gc.plan(640, 360, 3840, 2160, any_density=True) == (4, 1540 * 27)
     assert gc.plan(240, 135, 3840, 2160, any_density=True) == (16, 0)  # 4 rows would need 4100 x 60 bytes
+    # at most 65535 bands: 8 x 1000 -> 8 x 1048560 is 65535 bands of 16 rows, 8 x 1048700 would be 65544 and takes bands of
+    # ceil(1048700 / 65535) = 17 -> 20 rows with the 8 x 4 bytes of LDS sized for 16; the gather form is capped the same way
+    assert gc.plan(8, 1048560, 8, 1000) == (16, 32) and gc.plan(8, 1048561, 8, 1000) == (20, 32)
+    assert gc.plan(8, 1048700, 8, 1000) == (20, 32) and (1048700 + 19) // 20 == 52435
+    assert gc.plan(8, 1048700, 800, 100000) == (20, 0) and gc.plan(8, 65535 * 20 + 1, 8, 1000) == (24, 32)
 
 
 @pytest.mark.parametrize("case", gc.ALL_CHECKS, ids=lambda f: f.__name__[6:])
