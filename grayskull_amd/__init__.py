@@ -142,6 +142,8 @@ _SIGS = {
                                            C.c_uint, C.c_uint, C.c_uint]),
     "gsh_match_orb_dev": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p,
                                  C.c_void_p, C.c_uint, C.c_float]),
+    "gsh_match_orb_batch": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint,
+                                   C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_float]),
     "gsh_adaptive_threshold_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
                                             C.c_uint, C.c_int]),
     "gsh_filter_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
@@ -555,6 +557,25 @@ class Grayskull:
     def match_orb_dev(self, k1, n1, k2, n2, matches, count, max_matches, max_distance):
         self.c.gsh_match_orb_dev(_ptr(k1), n1, _ptr(k2), n2, _ptr(matches), _ptr(count),
                                  max_matches, max_distance)
+
+    @staticmethod
+    def _keypoint_sets(k):
+        """(cap, nset) of one (cap, 12) set of keypoint records or of nset sets (nset, cap, 12), int32"""
+        if k.ndim not in (2, 3) or int(k.shape[-1]) != 12:
+            raise ValueError("expected (cap, 12) or (nset, cap, 12) int32 keypoint records")
+        return int(k.shape[-2]), (1 if k.ndim == 2 else int(k.shape[0]))
+
+    def match_orb_batch(self, k1, n1, k2, n2, matches, counts, max_distance):
+        """gsh_match_orb_batch: pair p of n = len(counts) = gs_match_orb of query set p of k1 -- or its one set -- against
+        train set p of k2 -- or its one set; n1 / n2: per-set record counts (nset) read on the device, or None for all cap
+        records; matches (n, max_matches, 3) int32 {idx1, idx2, distance}, counts (n) -- device tensors, nothing comes back
+        to the host"""
+        cap1, nset1 = self._keypoint_sets(k1)
+        cap2, nset2 = self._keypoint_sets(k2)
+        if matches.ndim != 3 or int(matches.shape[2]) != 3 or int(matches.shape[0]) != int(counts.shape[0]):
+            raise ValueError("expected matches (n, max_matches, 3) and counts (n)")
+        self.c.gsh_match_orb_batch(_ptr(k1), cap1, _ptr(n1), nset1, _ptr(k2), cap2, _ptr(n2), nset2, int(matches.shape[0]),
+                                   _ptr(matches), _ptr(counts), int(matches.shape[1]), max_distance)
 
     def adaptive_threshold_batch(self, dst, src, radius, c):
         n, h, w = self._nhw(src)

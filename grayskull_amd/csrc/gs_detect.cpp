@@ -12,6 +12,7 @@
 #include "k_lbp.h"
 #include "k_lbp_tile.h"
 #include "k_orb.h"
+#include "k_match.h"
 
 namespace gsi {
 thread_local unsigned long long *g_lbp_evaluated = nullptr;
@@ -717,6 +718,40 @@ void launch_match(const uint32_t *k1, unsigned n1, const uint32_t *k2, unsigned 
                  MatchEmit{best, best + n1, matches});
 }
 
+/* gs_match_orb for n pairs (k_match.h): per launch one k_match_batch -- a block per 64 queries of a pair, whatever the
+ * device-side counts are; the blocks beyond a pair's count leave at once -- and the ordered, capped emit with the pair as
+ * its frame.  Scratch (mask words, chunk counters, 8 bytes per query slot) stays within kMatchScratch whatever n is: the
+ * pairs are worked through in groups, and a single pair that needs more is a group of its own. */
+constexpr size_t kMatchScratch = 64u << 20;
+void launch_match_batch(const uint32_t *k1, unsigned cap1, const unsigned *n1, unsigned nset1, const uint32_t *k2,
+                        unsigned cap2, const unsigned *n2, unsigned nset2, unsigned n, unsigned *matches,
+                        unsigned *counts, unsigned max_matches, float max_distance) {
+  hipStream_t st = ctx().s();
+  if (max_matches == 0) {
+    GS_HIP(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
+    return;
+  }
+  const unsigned words = (cap1 - 1u) / 64u + 1u, nchunks = (words + kChunkWords - 1) / kChunkWords;
+  const unsigned per1 = nset1 == 1 ? 0u : 1u, per2 = nset2 == 1 ? 0u : 1u;
+  const size_t mask_b = (size_t)nchunks * kChunkWords * 8, per_pair = mask_b + (size_t)nchunks * 8 + (size_t)cap1 * 8;
+  const unsigned group = (unsigned)std::min<size_t>(kMaxZ, std::max<size_t>(1, kMatchScratch / per_pair));
+  for (unsigned f0 = 0; f0 < n; f0 += group) {
+    const unsigned nn = std::min(group, n - f0);
+    unsigned long long *mask = (unsigned long long *)ctx().scratch(SL_MASK, (size_t)nn * mask_b);
+    unsigned *cnt = (unsigned *)ctx().scratch(SL_CNT, (size_t)nn * nchunks * 4);
+    unsigned *best = (unsigned *)ctx().scratch(SL_BEST, (size_t)nn * cap1 * 8);
+    unsigned *dist = best + (size_t)nn * cap1;
+    GS_HIP(hipMemsetAsync(mask, 0, (size_t)nn * mask_b, st));
+    GS_HIP(hipMemsetAsync(cnt, 0, (size_t)nn * nchunks * 4, st));
+    const uint32_t *q = k1 + (size_t)f0 * per1 * cap1 * 12u, *t = k2 + (size_t)f0 * per2 * cap2 * 12u;
+    const unsigned *nq = n1 ? n1 + (size_t)f0 * per1 : nullptr, *nt = n2 ? n2 + (size_t)f0 * per2 : nullptr;
+    GS_LAUNCH(k_match_batch, dim3(words, nn), dim3(64 * kMatchSlices), 0, st, q, cap1, nq, per1, t, cap2, nt, per2, max_distance, best,
+              dist, mask, cnt, nchunks);
+    run_compaction(mask, cnt, nchunks, nn, max_matches, counts + f0,
+                   MatchBatchEmit{best, dist, cap1, matches + (size_t)f0 * max_matches * 3u, max_matches});
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -939,6 +974,18 @@ void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct g
   GS_ASSERT(k1 && k2 && matches && count);
   launch_match((const uint32_t *)k1, n1, (const uint32_t *)k2, n2, (unsigned *)matches, count,
                max_matches, max_distance);
+}
+void gsh_match_orb_batch(const struct gs_keypoint *k1, unsigned cap1, const unsigned *n1, unsigned nset1,
+                         const struct gs_keypoint *k2, unsigned cap2, const unsigned *n2, unsigned nset2,
+                         unsigned n, struct gs_match *matches, unsigned *counts,
+                         unsigned max_matches, float max_distance) {
+  if (n == 0) return;
+  GS_ASSERT(k1 && k2 && matches && counts);
+  GS_ASSERT(cap1 > 0 && cap2 > 0);
+  GS_ASSERT(nset1 == 1 || nset1 == n);
+  GS_ASSERT(nset2 == 1 || nset2 == n);
+  launch_match_batch((const uint32_t *)k1, cap1, n1, nset1, (const uint32_t *)k2, cap2, n2, nset2, n,
+                     (unsigned *)matches, counts, max_matches, max_distance);
 }
 
 /* The reference re-reads the caller's tables on every call (ref :790-835), so a cascade edited in

@@ -229,6 +229,24 @@ void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct g
                        unsigned n2, struct gs_match *matches, unsigned *count,
                        unsigned max_matches, float max_distance);
 
+/* ---- descriptor matching over a batch (ref :680-699; docs/design/detectors.md "Descriptor matching over a batch") -----
+ * gs_match_orb for n pairs of keypoint sets in one launch.  All pointers device pointers, stream-ordered on the current
+ * stream, no host synchronisation and no read-back (the library's grow-only scratch synchronises once when it has to
+ * grow; it stays within 64 MiB whatever n is, unless a single pair needs more).  n == 0 returns before any check or launch.
+ * GS_ASSERT: non-NULL k1, k2, matches, counts; cap1, cap2 non-zero; nset1 == 1 || nset1 == n; nset2 == 1 || nset2 == n.
+ * Pair p takes its queries from set (nset1 == 1 ? 0 : p) of k1 -- the records at k1 + set * cap1, of which the first
+ * min(n1[set], cap1) count, all cap1 when n1 is NULL -- and its train set from k2, cap2, n2, nset2 in the same way.  n1 and
+ * n2 are read ON THE DEVICE: this is the layout gsh_orb_extract_batch_nostdlib leaves (cap = its nkps), so the two calls
+ * chain with nothing in between.  k1 and k2 may alias; neither is written.
+ * counts[p] and matches[p * max_matches ...] are what gs_match_orb(Q, nq, T, nt, out, max_matches, max_distance) returns
+ * and writes, bit for bit: the ratio test in float, the first index of the minimum, matches in ascending query order;
+ * the records at and beyond counts[p] are not written.  max_matches == 0 zeroes counts and does nothing else.
+ * matches needs 4-byte alignment only.  The pairs of a call are split at GSH_TUNE_FRAMES_PER_LAUNCH like every batch. */
+void gsh_match_orb_batch(const struct gs_keypoint *k1, unsigned cap1, const unsigned *n1, unsigned nset1,
+                         const struct gs_keypoint *k2, unsigned cap2, const unsigned *n2, unsigned nset2,
+                         unsigned n, struct gs_match *matches, unsigned *counts,
+                         unsigned max_matches, float max_distance);
+
 /* ---- "next" rows (ref :230, :255, :189) ------------------------------------------ */
 void gsh_adaptive_threshold_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h,
                                   unsigned n, unsigned radius, int c);
