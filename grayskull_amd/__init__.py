@@ -140,6 +140,10 @@ _SIGS = {
     "gsh_orb_pyramid_buffer_bytes": (C.c_size_t, [C.c_uint, C.c_uint, C.c_uint]),
     "gsh_orb_extract_pyramid": (C.c_uint, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
                                            C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_pyramid_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_orb_pyramid_batch_buffer_bytes": (C.c_size_t, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_orb_extract_pyramid_batch_nostdlib": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
     "gsh_match_orb_dev": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p,
                                  C.c_void_p, C.c_uint, C.c_float]),
     "gsh_match_orb_batch": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint,
@@ -553,6 +557,23 @@ class Grayskull:
         n = self.c.gsh_orb_extract_pyramid(_ptr(img), w, h, _ptr(buffer), kps.ctypes.data, nkps, threshold,
                                            n_levels)
         return kps[:n].copy()
+
+    def pyramid_batch(self, levels, imgs, n_levels):
+        """gsh_pyramid_batch: levels 1 .. L-1 of the n frames of imgs (n, h, w) into `levels`, a flat uint8 device buffer
+        of level planes (n frames each) back to back"""
+        n, h, w = self._nhw(imgs)
+        self.c.gsh_pyramid_batch(_ptr(levels), _ptr(imgs), w, h, n, n_levels)
+
+    def orb_pyramid_batch_buffer_bytes(self, w, h, n_levels, n):
+        return int(self.c.gsh_orb_pyramid_batch_buffer_bytes(w, h, n_levels, n))
+
+    def orb_extract_pyramid_batch_nostdlib(self, imgs, buffer, kps, counts, nkps, threshold, n_levels, level_counts=None):
+        """device-resident pyramid ORB (nanomagick.c:245-290, GS_NO_STDLIB trig): buffer orb_pyramid_batch_buffer_bytes
+        uint8, kps (n, nkps, 12) int32, counts (n) and level_counts (n, 4) or None -- device tensors, nothing comes back
+        to the host"""
+        n, h, w = self._nhw(imgs)
+        self.c.gsh_orb_extract_pyramid_batch_nostdlib(_ptr(imgs), w, h, n, _ptr(buffer), _ptr(kps), _ptr(counts),
+                                                      _ptr(level_counts), nkps, threshold, n_levels)
 
     def match_orb_dev(self, k1, n1, k2, n2, matches, count, max_matches, max_distance):
         self.c.gsh_match_orb_dev(_ptr(k1), n1, _ptr(k2), n2, _ptr(matches), _ptr(count),

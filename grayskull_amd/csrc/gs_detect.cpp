@@ -968,6 +968,58 @@ unsigned gsh_orb_extract_pyramid(const uint8_t *img_dev, unsigned w, unsigned h,
   }
   return total;
 }
+size_t gsh_orb_pyramid_batch_buffer_bytes(unsigned w, unsigned h, unsigned n_levels, unsigned n) {
+  return (size_t)n * gsh_orb_pyramid_buffer_bytes(w, h, n_levels);
+}
+/* ref examples/nanomagick/nanomagick.c:245-290 (reference built -DGS_NO_STDLIB) for n frames, no host round trip: the
+ * level planes in one launch (gsh_pyramid_batch), then per level FAST -> k_orb_select_level -> k_orb_describe_level on the
+ * one stream.  The first L-1 levels take `per` keypoints; the last takes what THIS frame's earlier levels left, a number
+ * that exists on the device only: its FAST pass runs with the largest cap a frame can need, min(4 * nkps, 5000), and the
+ * selection looks at the prefix the frame's own cap would have produced (launch_fast: the score pass does not see the cap;
+ * k_emit ranks the corners in scan order and emits rank < cap). */
+void gsh_orb_extract_pyramid_batch_nostdlib(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n,
+                                            uint8_t *buffer_dev, struct gs_keypoint *kps_dev, unsigned *counts_dev,
+                                            unsigned *level_counts_dev, unsigned nkps, unsigned threshold,
+                                            unsigned n_levels) {
+  if (n == 0) return;
+  GS_ASSERT(img_dev && buffer_dev && kps_dev && counts_dev && w > 0 && h > 0);
+  hipStream_t st = ctx().s();
+  unsigned lw[4], lh[4];
+  const unsigned L = orb_pyramid_dims(w, h, n_levels, lw, lh);
+  if (level_counts_dev) GS_HIP(hipMemsetAsync(level_counts_dev, 0, (size_t)n * 16, st));
+  if (L == 0 || nkps == 0 || w < 7 || h < 7) { /* the driver's level loop is empty (nanomagick.c:262, :276); gs_fast's loops are (ref :489) */
+    GS_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n * 4, st));
+    return;
+  }
+  gsh_pyramid_batch(buffer_dev, img_dev, w, h, n, L);
+  /* plane l of the levels / of the score maps: n frames of lw[l] x lh[l] */
+  const uint8_t *lev[4] = {img_dev, nullptr, nullptr, nullptr};
+  uint8_t *sm[4];
+  size_t fb[4], off = 0;
+  for (unsigned l = 0; l < L; l++) fb[l] = (size_t)lw[l] * lh[l];
+  for (unsigned l = 1; l < L; l++) lev[l] = buffer_dev + off, off += fb[l] * n;
+  for (unsigned l = 0; l < L; l++) sm[l] = buffer_dev + off, off += fb[l] * n;
+  const unsigned per = nkps / L, cap_last = std::min(nkps * 4u, 5000u);
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const unsigned nn = std::min(kMaxZ, n - f0);
+    unsigned *cand = (unsigned *)ctx().scratch(SL_KPS, (size_t)nn * cap_last * 48 + 16); /* the last level's: the largest */
+    unsigned *cnt = (unsigned *)ctx().scratch(SL_TOT, (size_t)nn * 4 + 16);
+    unsigned *lc = level_counts_dev ? level_counts_dev + 4 * (size_t)f0 : (unsigned *)ctx().scratch(SL_ORB_LEVELS, (size_t)nn * 16);
+    if (!level_counts_dev) GS_HIP(hipMemsetAsync(lc, 0, (size_t)nn * 16, st));
+    unsigned *out = (unsigned *)kps_dev + (size_t)f0 * nkps * 12;
+    for (unsigned l = 0; l < L; l++) {
+      const bool last = l + 1 == L;
+      if (!last && per == 0) continue; /* level_nkps == 0 (nanomagick.c:276): the level's score maps stay as they are */
+      const unsigned quota = last ? nkps : per; /* the last level's: an upper bound, k_orb_select_level has the frame's own */
+      const unsigned cap = std::min(quota * 4u, 5000u);
+      launch_fast(lev[l] + fb[l] * f0, sm[l] + fb[l] * f0, lw[l], lh[l], nn, cand, cnt, cap, threshold);
+      GS_LAUNCH(k_orb_select_level, dim3(nn), dim3(64), 0, st, (const unsigned *)cand, (const unsigned *)cnt, cap, lw[l], lh[l],
+                nkps, per, l, last ? 1u : 0u, out, lc, counts_dev + f0);
+      GS_LAUNCH(k_orb_describe_level, dim3(quota, nn), dim3(256), 0, st, lev[l] + fb[l] * f0, lw[l], lh[l], fb[l], out,
+                (const unsigned *)lc, nkps, l);
+    }
+  }
+}
 void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct gs_keypoint *k2,
                        unsigned n2, struct gs_match *matches, unsigned *count,
                        unsigned max_matches, float max_distance) {

@@ -82,7 +82,7 @@ namespace gsi {
 /* ------------------------------------------------------------------ per-thread context */
 enum Slot { SL_IN = 0, SL_OUT, SL_AUX, SL_AUX2, SL_II, SL_PAD, SL_MASK, SL_CNT, SL_PFX, SL_TOT, SL_PRE,
             SL_HISTP, SL_HIST, SL_THR, SL_KPS, SL_MOM, SL_KIN, SL_DESC, SL_TAB, SL_JUMP, SL_LEV,
-            SL_BEST, SL_NZ,
+            SL_BEST, SL_NZ, SL_ORB_LEVELS, /* per-frame level counts of gsh_orb_extract_pyramid_batch_nostdlib */
             SL_BLOB_BITS, SL_BLOB_PAR, SL_BLOB_STAT, SL_BLOB_ROW, SL_BLOB_LAB, SL_BLOB_REC, SL_COUNT }; /* gs_blobs.cpp */
 
 /* gsh_edge_pipeline_batch: frames per chunk (measured best for 64..512-frame batches of 4K frames:
@@ -387,6 +387,20 @@ inline bool strip_ok16(unsigned w, unsigned h, const void *a, const void *b) {
  * gsh_tune key 8 lowers it so that the splitting logic of every launcher can be exercised with a handful of frames */
 inline unsigned max_frames_per_launch() { return g_tune[8] > 0 ? (unsigned)g_tune[8] : 32768u; }
 #define kMaxZ (max_frames_per_launch())
+
+/* the levels of the ORB pyramid driver (ref examples/nanomagick/nanomagick.c:247-260): n_levels clamped to 4, halved
+ * (floor) per level, stopping before a level narrower or lower than 32.  -> L, with lw / lh [0, L) filled */
+inline unsigned orb_pyramid_dims(unsigned w, unsigned h, unsigned n_levels, unsigned lw[4], unsigned lh[4]) {
+  if (n_levels > 4) n_levels = 4;
+  if (n_levels == 0) return 0;
+  lw[0] = w, lh[0] = h;
+  for (unsigned l = 1; l < n_levels; l++) {
+    const unsigned nw = lw[l - 1] / 2, nh = lh[l - 1] / 2;
+    if (nw < 32 || nh < 32) return l;
+    lw[l] = nw, lh[l] = nh;
+  }
+  return n_levels;
+}
 
 #define GS_VALID(i) ((i).data && (i).w > 0 && (i).h > 0)
 

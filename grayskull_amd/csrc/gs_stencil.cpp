@@ -1015,6 +1015,28 @@ void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigne
   }
 }
 
+/* levels 1 .. L-1 of n frames in one launch per kMaxZ frames (k_pyramid); the level rule is the ORB driver's
+ * (nanomagick.c:247-260, orb_pyramid_dims) */
+void gsh_pyramid_batch(uint8_t *levels_dev, const uint8_t *img_dev, unsigned w, unsigned h, unsigned n, unsigned n_levels) {
+  if (n == 0) return;
+  GS_ASSERT(levels_dev && img_dev && w > 0 && h > 0);
+  unsigned lw[4], lh[4];
+  const unsigned L = orb_pyramid_dims(w, h, n_levels, lw, lh);
+  if (L <= 1) return;
+  hipStream_t st = ctx().s();
+  uint8_t *plane[4] = {nullptr, levels_dev, nullptr, nullptr};
+  size_t fb[4] = {(size_t)w * h, 0, 0, 0};
+  for (unsigned l = 1; l < 4; l++) {
+    fb[l] = l < L ? (size_t)lw[l] * lh[l] : 0;
+    if (l + 1 < 4) plane[l + 1] = plane[l] + fb[l] * n;
+  }
+  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
+    const unsigned nn = std::min(kMaxZ, n - f0);
+    GS_LAUNCH(k_pyramid, dim3(((w + 15) / 16 + 63) / 64, ((h + 7) / 8 + 3) / 4, nn), dim3(64, 4), 0, st, plane[1] + fb[1] * f0,
+              plane[2] + fb[2] * f0, plane[3] + fb[3] * f0, img_dev + fb[0] * f0, w, h, L);
+  }
+}
+
 void gsh_crop_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n, struct gs_rect roi) {
   if (n == 0) return;
   GS_ASSERT(dst && src && sw > 0 && sh > 0 && roi.w > 0 && roi.h > 0);

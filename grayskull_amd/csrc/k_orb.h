@@ -320,6 +320,156 @@ __global__ __launch_bounds__(256) void k_orb_describe(const uint8_t *img, unsign
   }
 }
 
+/* ------------------------------------------------------------------ pyramid ORB over a batch: quotas read on the device */
+/* k_orb_select for one level of the pyramid driver (ref examples/nanomagick/nanomagick.c:272-288), the frame's quota
+ * derived on the device.  lc: n x 4 level counts; frame f's records of this level start behind those of its earlier levels,
+ * off = lc[4f] + .. + lc[4f + level - 1], at out + (f * nkps + off) records.  Quota: `per` (the host's nkps / L), for the
+ * last level nkps - off ("the remainder", nanomagick.c:275).  gs_orb_extract with that quota asks gs_fast for
+ * min(4 * quota, 5000) candidates (ref :656): cand holds the first `cap` corners in scan order (k_emit ranks in scan order
+ * and drops rank >= cap), cap >= every frame's own, so the frame's list is the first min(count, 4 * quota, 5000) of them.
+ * Writes lc[4f + level], and for the last level out_count[f] = the frame's total.  The selection itself is k_orb_select's.
+ * grid n frames, block 64. */
+__global__ __launch_bounds__(64) void k_orb_select_level(const unsigned *cand, const unsigned *cand_count, unsigned cap,
+                                                        unsigned w, unsigned h, unsigned nkps, unsigned per, unsigned level,
+                                                        unsigned last, unsigned *out, unsigned *lc, unsigned *out_count) {
+  __shared__ unsigned cnt[256], base[256];
+  const unsigned lane = threadIdx.x, f = blockIdx.x, r = 15u;
+  unsigned off = 0;
+  for (unsigned k = 0; k < level; k++) off += lc[4u * f + k];
+  const unsigned want = last ? nkps - off : per;
+  const unsigned own_cap = want * 4u < 5000u ? want * 4u : 5000u; /* GS_MIN(nkps * 4, 5000), unsigned like ref :656 */
+  unsigned n = cand_count[f] < cap ? cand_count[f] : cap;
+  n = n < own_cap ? n : own_cap;
+  const unsigned *c = cand + (size_t)f * cap * 12u;
+  unsigned *o = out + ((size_t)f * nkps + off) * 12u;
+  for (unsigned i = lane; i < 256u; i += 64u) cnt[i] = 0;
+  __syncthreads();
+  constexpr unsigned U = 8;
+  for (unsigned i0 = 0; i0 < n; i0 += 64u * U) { /* wave-uniform */
+    unsigned x[U], y[U], resp[U];
+#pragma unroll
+    for (unsigned u = 0; u < U; u++) {
+      const unsigned i = i0 + 64u * u + lane, ic = i < n ? i : n - 1u;
+      x[u] = c[(size_t)ic * 12u], y[u] = c[(size_t)ic * 12u + 1], resp[u] = c[(size_t)ic * 12u + 2] & 255u;
+    }
+#pragma unroll
+    for (unsigned u = 0; u < U; u++)
+      if (i0 + 64u * u + lane < n && x[u] >= r && y[u] >= r && x[u] < w - r && y[u] < h - r) atomicAdd(&cnt[resp[u]], 1u);
+  }
+  __syncthreads();
+  {
+    unsigned own[4], tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) own[k] = cnt[255u - (lane * 4u + (unsigned)k)], tot += own[k];
+    unsigned run = wave_incl_scan(tot) - tot;
+    const unsigned total = readlane_last(wave_incl_scan(tot));
+#pragma unroll
+    for (int k = 0; k < 4; k++) base[255u - (lane * 4u + (unsigned)k)] = run, run += own[k];
+    if (lane == 0) {
+      const unsigned got = total < want ? total : want;
+      lc[4u * f + level] = got;
+      if (last) out_count[f] = off + got;
+    }
+  }
+  __syncthreads();
+  for (unsigned j0 = 0; j0 < n; j0 += 64u * U) { /* wave-uniform */
+    unsigned xs[U], ys[U], rs[U];
+#pragma unroll
+    for (unsigned u = 0; u < U; u++) {
+      const unsigned i = j0 + 64u * u + lane, ic = i < n ? i : n - 1u;
+      xs[u] = c[(size_t)ic * 12u], ys[u] = c[(size_t)ic * 12u + 1], rs[u] = c[(size_t)ic * 12u + 2];
+    }
+#pragma unroll
+    for (unsigned u = 0; u < U; u++) { /* the trips in scan order */
+      if (j0 + 64u * u >= n) break; /* wave-uniform */
+      const unsigned x = xs[u], y = ys[u], resp = rs[u];
+      const bool ok = j0 + 64u * u + lane < n && x >= r && y >= r && x < w - r && y < h - r;
+      const unsigned rv = resp & 255u;
+      uint64_t same = ballot(ok);
+#pragma unroll
+      for (unsigned b = 0; b < 8u; b++) {
+        const bool bit = ((rv >> b) & 1u) != 0u;
+        const uint64_t m = ballot(ok && bit);
+        same &= bit ? m : ~m;
+      }
+      const unsigned start = base[ok ? rv : 0u];
+      const unsigned before = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
+      const unsigned rank = ok ? start + before : 0xffffffffu;
+      __syncthreads(); /* every lane has read base[] */
+      if (ok && before == 0u) base[rv] = start + (unsigned)__popcll(same);
+      __syncthreads();
+      if (ok && rank < want) {
+        unsigned *q = o + (size_t)rank * 12u;
+        q[0] = x, q[1] = y, q[2] = resp;
+#pragma unroll
+        for (int k = 3; k < 12; k++) q[k] = 0;
+      }
+    }
+  }
+}
+
+/* k_orb_describe for one level: block k of frame f takes record off + k of the frame's list (off as in k_orb_select_level),
+ * k < lc[4f + level]; the patch is read from the level's plane at the record's unscaled coordinates, which are then
+ * shifted left by the level (nanomagick.c:282-286).  grid (the level's largest quota, n frames), block 256. */
+__global__ __launch_bounds__(256) void k_orb_describe_level(const uint8_t *img, unsigned w, unsigned h, size_t frame_bytes,
+                                                           unsigned *kps, const unsigned *lc, unsigned nkps, unsigned level) {
+#ifndef GS_EMU
+#pragma clang fp contract(off)
+#endif
+  __shared__ int part[2][4];
+  __shared__ float trig[2];
+  const unsigned f = blockIdx.y, k = blockIdx.x, i = threadIdx.x;
+  if (k >= lc[4u * f + level]) return; /* whole block */
+  unsigned off = 0;
+  for (unsigned j = 0; j < level; j++) off += lc[4u * f + j];
+  img += (size_t)f * frame_bytes;
+  unsigned *kp = kps + ((size_t)f * nkps + off + k) * 12u;
+  const unsigned x = kp[0], y = kp[1];
+  const int r = 15, side = 2 * r + 1, total = side * side;
+  const PxReader px(img, w, h);
+  int m01 = 0, m10 = 0;
+  px.with([&](auto SM) {
+    int I[4], dyv[4], dxv[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int t = (int)i + 256 * u;
+      dyv[u] = t / side - r, dxv[u] = t % side - r;
+      const unsigned sx = x + (unsigned)dxv[u], sy = y + (unsigned)dyv[u];
+      I[u] = (int)px.template get<decltype(SM)::value>(sx, sy, t < total && dxv[u] * dxv[u] + dyv[u] * dyv[u] <= r * r);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) m01 += dyv[u] * I[u], m10 += dxv[u] * I[u];
+  });
+  m01 = wave_sum_i(m01), m10 = wave_sum_i(m10);
+  if ((i & 63u) == 0) part[0][i >> 6] = m01, part[1][i >> 6] = m10;
+  __syncthreads(); /* every thread has used the record's x and y */
+  if (i == 0) {
+    const int a = part[0][0] + part[0][1] + part[0][2] + part[0][3], b = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+    const float angle = gs_atan2_poly((float)a, (float)b);                  /* ref :620 */
+    kp[3] = __builtin_bit_cast(uint32_t, angle);
+    trig[0] = gs_sin_poly(angle), trig[1] = gs_sin_poly((float)(angle + 1.57079f)); /* ref :626 */
+    if (level) kp[0] = x << level, kp[1] = y << level;
+  }
+  __syncthreads();
+  const float sin_a = trig[0], cos_a = trig[1];
+  const int p0 = k_brief_pattern[4 * i], p1 = k_brief_pattern[4 * i + 1];
+  const int p2 = k_brief_pattern[4 * i + 2], p3 = k_brief_pattern[4 * i + 3];
+  const float m00 = (float)p0 * cos_a, m01f = (float)p1 * sin_a;
+  const float m10f = (float)p0 * sin_a, m11 = (float)p1 * cos_a;
+  const float n00 = (float)p2 * cos_a, n01 = (float)p3 * sin_a;
+  const float n10 = (float)p2 * sin_a, n11 = (float)p3 * cos_a;
+  const float dx1 = m00 - m01f, dy1 = m10f + m11, dx2 = n00 - n01, dy2 = n10 + n11;
+  const unsigned x1 = (unsigned)((int)x + (int)dx1), y1 = (unsigned)((int)y + (int)dy1);
+  const unsigned x2 = (unsigned)((int)x + (int)dx2), y2 = (unsigned)((int)y + (int)dy2);
+  unsigned I1 = 0, I2 = 0;
+  px.with([&](auto SM) { I1 = px.template get<decltype(SM)::value>(x1, y1), I2 = px.template get<decltype(SM)::value>(x2, y2); });
+  const uint64_t m = ballot(I1 > I2);
+  if (lane_id() == 0) {
+    const unsigned wv = i >> 6;
+    kp[4 + 2 * wv] = (uint32_t)m, kp[4 + 2 * wv + 1] = (uint32_t)(m >> 32);
+  }
+}
+
 /* keypoint record = 12 dwords, descriptor at dword 4 (grayskull.h:42-47).
  * One WAVE per query: the 64 lanes stride over the train descriptors, each keeping the
  * reference's (best, second, first-argmin) state; states merge with

@@ -394,5 +394,104 @@ __global__ __launch_bounds__(256) void k_downsample8(uint8_t *dst, const uint8_t
   store_u32x2_any(dst + (size_t)blockIdx.z * ((size_t)dw * dh) + (size_t)y * dw + ox, o[0], o[1]);
 }
 
+/* 4 px of two rows -> their two 2x2 means, in the low two bytes (the u16-pair sums of k_downsample8) */
+GS_DEV uint32_t downsample_quad(uint32_t da, uint32_t db) {
+  const uint32_t v01 = add2(unpack_lo(da), unpack_lo(db)), v23 = add2(unpack_hi(da), unpack_hi(db));
+  const uint32_t s0 = (v01 & 0xffffu) + (v01 >> 16), s1 = (v23 & 0xffffu) + (v23 >> 16);
+  return (s0 >> 2) | ((s1 >> 2) << 8);
+}
+/* the low nb bytes of v at any address: 4 and 2 as one store, anything else byte by byte */
+GS_DEV void store_bytes_any(uint8_t *p, uint32_t v, unsigned nb) {
+#ifdef GS_EMU
+  memcpy(p, &v, nb);
+#else
+  typedef uint32_t u32_a1 __attribute__((aligned(1)));
+  typedef uint16_t u16_a1 __attribute__((aligned(1)));
+  if (nb == 4u) *(u32_a1 *)p = v;
+  else if (nb == 2u) *(u16_a1 *)p = (uint16_t)v;
+  else
+    for (unsigned k = 0; k < nb; k++) p[k] = (uint8_t)(v >> (8u * k));
+#endif
+}
+
+/* Levels 1 .. nl-1 of the ORB pyramid (gs_downsample applied 1, 2, 3 times, ref :189-197) from ONE read of level 0.  w / 2
+ * floors at every level, so a level-l pixel is made of the aligned 2^l x 2^l source block under it and of nothing else: a
+ * lane owns 16 source px x 8 rows (eight 16-byte loads, requested together) and forms from them 8 x 4 pixels of level 1,
+ * 4 x 2 of level 2 and 2 x 1 of level 3 in registers, each level rounded (sum / 4) before the next is formed from it.  No
+ * LDS, no cross-lane traffic; frame bases and rows at any alignment.
+ * Edges: the groups must stay aligned to 16 source px for the deeper levels (no anchoring at the row's end as in
+ * k_downsample8).  Rows past the frame's last are read from the last row and their results not stored; a lane whose 16
+ * columns cross the row's end reads byte by byte from clamped columns and stores only the pixels its levels have.
+ * d1 / d2 / d3: the planes of levels 1 / 2 / 3, gridDim.z frames back to back each (d2, d3 unused below nl = 3, 4).
+ * grid (ceil(ceil(w/16)/64), ceil(ceil(h/8)/4), n), block (64,4) */
+__global__ __launch_bounds__(256) void k_pyramid(uint8_t *d1, uint8_t *d2, uint8_t *d3, const uint8_t *src, unsigned w,
+                                                 unsigned h, unsigned nl) {
+  const unsigned gx = blockIdx.x * 64u + threadIdx.x, gy = blockIdx.y * 4u + threadIdx.y;
+  if (gx * 16u >= w || gy * 8u >= h) return;
+  const unsigned lw[3] = {w / 2, w / 4, w / 8}, lh[3] = {h / 2, h / 4, h / 8};
+  const uint8_t *f = src + (size_t)blockIdx.z * ((size_t)w * h);
+  const bool whole = gx * 16u + 16u <= w;
+  uint32_t R[8][4];
+#pragma unroll
+  for (unsigned r = 0; r < 8u; r++) {
+    const unsigned y = gy * 8u + r < h ? gy * 8u + r : h - 1u;
+    const uint8_t *row = f + (size_t)y * w;
+    if (whole) {
+      const U4 v = load_u32x4_any(row + gx * 16u);
+      R[r][0] = v.x, R[r][1] = v.y, R[r][2] = v.z, R[r][3] = v.w;
+    } else {
+#pragma unroll
+      for (unsigned q = 0; q < 4u; q++) {
+        uint32_t d = 0;
+#pragma unroll
+        for (unsigned k = 0; k < 4u; k++) {
+          const unsigned x = gx * 16u + 4u * q + k;
+          d |= (uint32_t)row[x < w ? x : w - 1u] << (8u * k);
+        }
+        R[r][q] = d;
+      }
+    }
+  }
+  uint32_t A[4][2], B[2], C1;
+#pragma unroll
+  for (unsigned r = 0; r < 4u; r++)
+#pragma unroll
+    for (unsigned q = 0; q < 2u; q++)
+      A[r][q] = downsample_quad(R[2 * r][2 * q], R[2 * r + 1][2 * q]) | (downsample_quad(R[2 * r][2 * q + 1], R[2 * r + 1][2 * q + 1]) << 16);
+#pragma unroll
+  for (unsigned r = 0; r < 2u; r++) B[r] = downsample_quad(A[2 * r][0], A[2 * r + 1][0]) | (downsample_quad(A[2 * r][1], A[2 * r + 1][1]) << 16);
+  C1 = downsample_quad(B[0], B[1]);
+  /* level l: a lane's (8 >> l) px x (4 >> l) rows at (gx * (8 >> l), gy * (4 >> l)) */
+  {
+    uint8_t *o = d1 + (size_t)blockIdx.z * ((size_t)lw[0] * lh[0]);
+    const unsigned x0 = gx * 8u, nx = x0 >= lw[0] ? 0u : (lw[0] - x0 < 8u ? lw[0] - x0 : 8u);
+#pragma unroll
+    for (unsigned r = 0; r < 4u; r++) {
+      const unsigned y = gy * 4u + r;
+      if (y >= lh[0] || nx == 0u) continue;
+      uint8_t *p = o + (size_t)y * lw[0] + x0;
+      if (nx == 8u) store_u32x2_any(p, A[r][0], A[r][1]);
+      else {
+        store_bytes_any(p, A[r][0], nx < 4u ? nx : 4u);
+        if (nx > 4u) store_bytes_any(p + 4, A[r][1], nx - 4u);
+      }
+    }
+  }
+  if (nl > 2u) {
+    uint8_t *o = d2 + (size_t)blockIdx.z * ((size_t)lw[1] * lh[1]);
+    const unsigned x0 = gx * 4u, nx = x0 >= lw[1] ? 0u : (lw[1] - x0 < 4u ? lw[1] - x0 : 4u);
+#pragma unroll
+    for (unsigned r = 0; r < 2u; r++) {
+      const unsigned y = gy * 2u + r;
+      if (y < lh[1] && nx) store_bytes_any(o + (size_t)y * lw[1] + x0, B[r], nx);
+    }
+  }
+  if (nl > 3u) {
+    uint8_t *o = d3 + (size_t)blockIdx.z * ((size_t)lw[2] * lh[2]);
+    const unsigned x0 = gx * 2u, nx = x0 >= lw[2] ? 0u : (lw[2] - x0 < 2u ? lw[2] - x0 : 2u);
+    if (gy < lh[2] && nx) store_bytes_any(o + (size_t)gy * lw[2] + x0, C1, nx);
+  }
+}
+
 }  // namespace gs
 #endif

@@ -223,6 +223,37 @@ unsigned gsh_orb_extract_pyramid(const uint8_t *img_dev, unsigned w, unsigned h,
                                  struct gs_keypoint *kps_host, unsigned nkps, unsigned threshold,
                                  unsigned n_levels);
 
+/* ---- pyramid ORB over a batch (docs/design/detectors.md "Pyramid ORB over a batch") ----------------------------------
+ * levels 1 .. L-1 of n frames, L as the ORB driver counts it (n_levels clamped to 4, stop before a level narrower or
+ * lower than 32): plane l holds n frames of lw[l] x lh[l] back to back, planes back to back in level order.  Frame f
+ * of plane l is gs_downsample applied l times to frame f, byte for byte.  ONE launch per kMaxZ frames
+ * (GSH_TUNE_FRAMES_PER_LAUNCH).  L <= 1 writes nothing.  Device pointers at any alignment, stream-ordered; n == 0
+ * returns before any check or launch; GS_ASSERT: non-NULL levels_dev and img_dev, w and h non-zero. */
+void gsh_pyramid_batch(uint8_t *levels_dev, const uint8_t *img_dev, unsigned w, unsigned h, unsigned n, unsigned n_levels);
+
+size_t gsh_orb_pyramid_batch_buffer_bytes(unsigned w, unsigned h, unsigned n_levels, unsigned n);  /* = n * gsh_orb_pyramid_buffer_bytes */
+
+/* extract_pyramid_orb_nm (examples/nanomagick/nanomagick.c:245-290) of a reference built -DGS_NO_STDLIB for n frames of
+ * one size.  All pointers device pointers, stream-ordered on the current stream, no host synchronisation and no read-back
+ * (the grow-only scratch may synchronise once when it grows).  n == 0 returns before any check or launch.  GS_ASSERT:
+ * non-NULL img_dev, buffer_dev, kps_dev, counts_dev; w and h non-zero.
+ * buffer_dev: gsh_orb_pyramid_batch_buffer_bytes bytes in gsh_orb_extract_pyramid's layout with every plane replaced by
+ * n planes, level-major: the level planes 1 .. L-1 as gsh_pyramid_batch writes them, then the score-map planes 0 .. L-1 of
+ * n frames each (n == 1: the single-frame layout).  The score maps' bytes are the caller's: only their interior is written,
+ * the 3-px frames are read by the NMS (ref :524) and never written.
+ * Frame f's result is what extract_pyramid_orb_nm(frame f, kps, nkps, threshold, buf_f, n_levels) returns and writes, buf_f
+ * being frame f's planes laid out as one buffer: per = nkps / L keypoints from each level l < L-1 (skipped, score maps
+ * untouched, when per == 0), nkps - (what the earlier levels of THIS frame produced) from the last; each level is
+ * gs_orb_extract of the level's image with that quota (FAST cap min(4 * quota, 5000)), coordinates shifted left by the
+ * level.  The records lie back to back in level order at kps_dev + f * nkps, counts_dev[f] is their number, records at and
+ * beyond it are not written.  level_counts_dev (n x 4, may be NULL): level l's share at [4 * f + l]; all four words are
+ * written, 0 for levels not run.  n_levels == 0, nkps == 0, w < 7 or h < 7: counts_dev (and level_counts_dev) are zeroed
+ * and nothing else is touched.  The output is the layout gsh_match_orb_batch reads (cap = nkps, n1 = counts_dev). */
+void gsh_orb_extract_pyramid_batch_nostdlib(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n,
+                                            uint8_t *buffer_dev, struct gs_keypoint *kps_dev, unsigned *counts_dev,
+                                            unsigned *level_counts_dev /* n x 4, may be NULL */,
+                                            unsigned nkps, unsigned threshold, unsigned n_levels);
+
 /* All pointers device; matches: max_matches records, the first *count written, the rest not; count: 1 u32.
  * Stream-ordered. */
 void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct gs_keypoint *k2,
