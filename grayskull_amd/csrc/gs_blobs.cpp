@@ -33,8 +33,7 @@ static void launch_blobs(const uint8_t *img, unsigned w, unsigned h, unsigned n,
   unsigned *rowpre = rowcnt + (size_t)G * h, *info = rowpre + (size_t)G * h;
   hipStream_t st = ctx().s();
   const dim3 rows((h + 3u) / 4u);
-  for (unsigned f0 = 0; f0 < n; f0 += G) {
-    const unsigned nn = std::min(G, n - f0);
+  for_frames(n, G, [&](unsigned f0, unsigned nn) {
     const uint8_t *im = img + np * f0;
     uint16_t *lab = labels + np * f0;
     GS_HIP(hipMemsetAsync(stats, 0, (size_t)nn * nslot * kBlobSlot * 4u, st));
@@ -53,43 +52,38 @@ static void launch_blobs(const uint8_t *img, unsigned w, unsigned h, unsigned n,
               (const unsigned *)par, lab, stats, nslot);
     GS_LAUNCH(k_blob_compact, dim3(nn), dim3(1024), 0, st, (const unsigned *)stats, nslot, cap, wrap, (const unsigned *)info,
               blobs + stride * f0, stride, counts + f0);
-  }
+  });
 }
 
 static void launch_corners(const uint8_t *img, const uint16_t *labels, unsigned w, unsigned h, unsigned n, const BlobRec *blobs,
                            uint32_t *corners) {
-  const unsigned G = std::min(kMaxZ, n);
-  unsigned long long *keys = (unsigned long long *)ctx().scratch(SL_BLOB_ROW, (size_t)G * kCornerKeys * 8u);
+  unsigned long long *keys = (unsigned long long *)ctx().scratch(SL_BLOB_ROW, (size_t)std::min(kMaxZ, n) * kCornerKeys * 8u);
   hipStream_t st = ctx().s();
   const size_t np = (size_t)w * h;
   const unsigned nb = std::min((h + 3u) / 4u, 128u); /* blocks per frame: waves stride over the rows of the box */
-  for (unsigned f0 = 0; f0 < n; f0 += G) {
-    const unsigned nn = std::min(G, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     GS_LAUNCH(k_corners_init, dim3(nn), dim3(64), 0, st, keys);
     GS_LAUNCH(k_corners, dim3(nb, nn), dim3(256), 0, st, img + np * f0, labels + np * f0, w, h, blobs + f0, keys);
     GS_LAUNCH(k_corners_final, dim3(nn), dim3(64), 0, st, (const unsigned long long *)keys, blobs + f0, corners + (size_t)8u * f0);
-  }
+  });
 }
 
 static void launch_perspective(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t *src, unsigned sw, unsigned sh, unsigned n,
                                const uint32_t *corners) {
   hipStream_t st = ctx().s();
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    GS_LAUNCH(k_perspective, grid2d(dw, dh, nn), dim3(64, 4), 0, st, dst + (size_t)dw * dh * f0, dw, dh,
-              src + (size_t)sw * sh * f0, sw, sh, corners + (size_t)8u * f0);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_perspective, grid2d(dw, dh, nn), dim3(64, 4), 0, st, dst + (size_t)dw * dh * f0, dw, dh, src + (size_t)sw * sh * f0, sw, sh,
+              corners + (size_t)8u * f0);
+  });
 }
 
 static void launch_largest(const BlobRec *blobs, unsigned nblobs, const unsigned *counts, unsigned n, BlobRec *largest,
                            unsigned *index) {
   hipStream_t st = ctx().s();
   const dim3 block(nblobs <= 4096u ? 64u : 256u); /* one wave per frame; a block for long record lists */
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    GS_LAUNCH(k_blob_largest, dim3(nn), block, 0, st, blobs + (size_t)nblobs * f0, nblobs, counts + f0, largest + f0,
-              index ? index + f0 : nullptr);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_blob_largest, dim3(nn), block, 0, st, blobs + (size_t)nblobs * f0, nblobs, counts + f0, largest + f0, index ? index + f0 : nullptr);
+  });
 }
 
 /* rows per band of k_blob_paint: about 32 KB of pixels per block (eight 16-byte steps per lane), fewer while the launch
@@ -100,7 +94,7 @@ static unsigned paint_band_rows(unsigned w, unsigned h, unsigned n) {
   const unsigned fit = (kPaintBits - 15u) / w;
   unsigned R = (32768u + w - 1u) / w;
   while (R > 1u && (size_t)n * ((h + R - 1u) / R) < (size_t)4u * topo().cus) R = (R + 1u) / 2u;
-  if (g_tune[0] > 0) R = (unsigned)g_tune[0];
+  if (g_tune[GSH_TUNE_STRIP_BAND_ROWS] > 0) R = (unsigned)g_tune[GSH_TUNE_STRIP_BAND_ROWS];
   return std::max(1u, std::min(std::min(R, fit), h));
 }
 
@@ -109,8 +103,7 @@ static void launch_paint(uint8_t *dst, const uint8_t *img, unsigned w, unsigned 
   hipStream_t st = ctx().s();
   const size_t np = (size_t)w * h;
   const unsigned R = paint_band_rows(w, h, n);
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     uint8_t *d = dst + np * f0;
     const uint8_t *s = img + np * f0;
     const BlobRec *b = blobs + (size_t)nblobs * f0;
@@ -121,7 +114,7 @@ static void launch_paint(uint8_t *dst, const uint8_t *img, unsigned w, unsigned 
       GS_LAUNCH(k_blob_paint_base, dim3(bx, nn), dim3(256), 0, st, d, s, np);
       GS_LAUNCH(k_blob_paint_fill, dim3(std::min(nblobs, 1024u), nn), dim3(256), 0, st, d, s, w, h, b, nblobs, counts + f0);
     }
-  }
+  });
 }
 
 }  // namespace gsi
@@ -134,16 +127,16 @@ unsigned gs_blobs(struct gs_image img, gs_label *labels, struct gs_blob *blobs, 
   GS_ASSERT((unsigned long long)img.w * img.h <= 0xffffffffull); /* pixel indices are u32 (so are the reference's) */
   const size_t np = (size_t)img.w * img.h;
   const unsigned cap = std::min(nblobs, kBlobCapMax);
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, np, SL_IN);
-  const bool lhost = !is_dev(labels), bhost = !is_dev(blobs);
-  uint16_t *l = lhost ? (uint16_t *)ctx().scratch(SL_BLOB_LAB, np * 2u) : labels;
+  const uint8_t *s = stage_in(img.data, np, SL_IN);
+  const Staged<uint16_t> l(labels, np * 2u, SL_BLOB_LAB);
+  const bool bhost = !is_dev(blobs);
   char *rec = (char *)ctx().scratch(SL_BLOB_REC, 16u + (bhost ? (size_t)cap * sizeof(BlobRec) : 0u));
   unsigned *count = (unsigned *)rec;
   BlobRec *b = bhost ? (BlobRec *)(rec + 16) : (BlobRec *)blobs;
-  launch_blobs(s, img.w, img.h, 1, l, b, cap, count, nblobs);
+  launch_blobs(s, img.w, img.h, 1, l.dev, b, cap, count, nblobs);
   unsigned *m = (unsigned *)ctx().pinned(Ctx::PIN_A, sizeof(unsigned));
   GS_HIP(hipMemcpyAsync(m, count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx().s()));
-  if (lhost) GS_HIP(hipMemcpyAsync(labels, l, np * 2u, hipMemcpyDeviceToHost, ctx().s()));
+  l.back();
   ctx().sync();
   const unsigned nb = *m;
   /* records [m, nblobs) are not written (the reference leaves stale provisional data there) */
@@ -157,26 +150,18 @@ unsigned gs_blobs(struct gs_image img, gs_label *labels, struct gs_blob *blobs, 
 void gs_blob_corners(struct gs_image img, gs_label *labels, struct gs_blob *b, struct gs_point c[4]) { /* ref :404 */
   GS_ASSERT(GS_VALID(img) && b && labels);
   const size_t np = (size_t)img.w * img.h;
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, np, SL_IN);
-  const uint16_t *l = (const uint16_t *)stage_in(labels, np * 2u, SL_BLOB_LAB);
+  const uint8_t *s = stage_in(img.data, np, SL_IN);
+  const uint16_t *l = stage_in(labels, np * 2u, SL_BLOB_LAB);
   const BlobRec *bd = (const BlobRec *)stage_in(b, sizeof(BlobRec), SL_BLOB_REC);
-  const bool chost = !is_dev(c);
-  uint32_t *cd = chost ? (uint32_t *)ctx().scratch(SL_BLOB_STAT, 4u * sizeof(struct gs_point)) : (uint32_t *)c;
-  launch_corners(s, l, img.w, img.h, 1, bd, cd);
-  if (chost) GS_HIP(hipMemcpyAsync(c, cd, 4u * sizeof(struct gs_point), hipMemcpyDeviceToHost, ctx().s()));
-  finish(chost);
+  const Staged<uint32_t> cd((uint32_t *)c, 4u * sizeof(struct gs_point), SL_BLOB_STAT);
+  launch_corners(s, l, img.w, img.h, 1, bd, cd.dev);
+  cd.done();
 }
 
 void gs_perspective_correct(struct gs_image dst, struct gs_image src, struct gs_point c[4]) { /* ref :423 */
   GS_ASSERT(GS_VALID(dst) && GS_VALID(src));
-  const size_t sb = (size_t)src.w * src.h, db = (size_t)dst.w * dst.h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, sb, SL_IN);
   const uint32_t *cd = (const uint32_t *)stage_in(c, 4u * sizeof(struct gs_point), SL_BLOB_REC);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, db) : dst.data;
-  launch_perspective(d, dst.w, dst.h, s, src.w, src.h, 1, cd);
-  if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, db, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { launch_perspective(d, dst.w, dst.h, s, src.w, src.h, 1, cd); });
 }
 
 /* ---- device-resident batches -------------------------------------------------------------------------------------- */

@@ -21,26 +21,22 @@ static unsigned long long move_cap(unsigned w, unsigned h) {
 
 static void launch_trace(const uint8_t *img, uint8_t *visited, unsigned w, unsigned h, unsigned n, ContourRec *recs, unsigned per_frame,
                          const unsigned *counts, uint8_t *status) {
-  const unsigned G = std::min(kMaxZ, n);
   const size_t np = (size_t)w * h;
   hipStream_t st = ctx().s();
-  for (unsigned f0 = 0; f0 < n; f0 += G) {
-    const unsigned nn = std::min(G, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     GS_LAUNCH(k_contour_trace, dim3(nn), dim3(64), 0, st, img + np * f0, visited + np * f0, w, h, recs + (size_t)per_frame * f0, per_frame,
               counts ? counts + f0 : (const unsigned *)nullptr, status ? status + (size_t)per_frame * f0 : (uint8_t *)nullptr, move_cap(w, h));
-  }
+  });
 }
 
 static void launch_starts(const uint16_t *labels, unsigned w, unsigned h, unsigned n, const uint32_t *blobs, unsigned nblobs,
                           const unsigned *counts, ContourRec *recs) {
-  const unsigned G = std::min(kMaxZ, n);
   const size_t np = (size_t)w * h;
   hipStream_t st = ctx().s();
-  for (unsigned f0 = 0; f0 < n; f0 += G) {
-    const unsigned nn = std::min(G, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     GS_LAUNCH(k_contour_starts, dim3((nblobs + 3u) / 4u, nn), dim3(256), 0, st, labels + np * f0, w, h, blobs + (size_t)nblobs * kContourBlobWords * f0, nblobs,
               counts ? counts + f0 : (const unsigned *)nullptr, recs + (size_t)nblobs * f0);
-  }
+  });
 }
 
 }  // namespace gsi
@@ -56,16 +52,14 @@ void gs_trace_contour(struct gs_image img, struct gs_image visited, struct gs_co
   GS_ASSERT(c != NULL);
   GS_ASSERT(img.w <= 0x7fffffffu && img.h <= 0x7fffffffu); /* the reference compares coordinates as int */
   const size_t np = (size_t)img.w * img.h;
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, np, SL_IN);
-  const bool vhost = !is_dev(visited.data);
-  uint8_t *v = vhost ? (uint8_t *)ctx().scratch(SL_OUT, np) : visited.data;
-  if (vhost) GS_HIP(hipMemcpyAsync(v, visited.data, np, hipMemcpyHostToDevice, ctx().s()));
+  const uint8_t *s = stage_in(img.data, np, SL_IN);
+  const Staged<uint8_t> v(visited.data, np, SL_OUT, /*copy_in=*/true);
   ContourRec *rec = (ContourRec *)ctx().scratch(SL_BLOB_REC, sizeof(ContourRec));
   ContourRec *back = (ContourRec *)ctx().pinned(Ctx::PIN_A, sizeof(ContourRec));
   GS_HIP(hipMemcpyAsync(rec, c, sizeof(ContourRec), hipMemcpyHostToDevice, ctx().s()));
-  launch_trace(s, v, img.w, img.h, 1, rec, 1, nullptr, nullptr);
+  launch_trace(s, v.dev, img.w, img.h, 1, rec, 1, nullptr, nullptr);
   GS_HIP(hipMemcpyAsync(back, rec, sizeof(ContourRec), hipMemcpyDeviceToHost, ctx().s()));
-  if (vhost) GS_HIP(hipMemcpyAsync(visited.data, v, np, hipMemcpyDeviceToHost, ctx().s()));
+  v.back();
   ctx().sync();
   c->box.x = back->bx, c->box.y = back->by, c->box.w = back->bw, c->box.h = back->bh;
   c->length = back->length;

@@ -45,7 +45,7 @@ void run_compaction(unsigned long long *mask, unsigned *cnt, unsigned nchunks, u
  * which also leaves the bitmap of scored pixels for the sparse NMS pass.  Thresholds above 0xffffff00 (p + t wraps in 32 bits)
  * and gsh_tune key 7 = 2 take k_fast_score_px: one global byte load per ring pixel, the literal form of ref :491-513.
  * Returns whether the bitmap was written. */
-bool fast_score_leaves_bitmap(unsigned threshold) { return g_tune[7] != 2 && threshold <= 0xffffff00u; }
+bool fast_score_leaves_bitmap(unsigned threshold) { return g_tune[GSH_TUNE_FAST_SCORE] != 2 && threshold <= 0xffffff00u; }
 bool launch_fast_score(hipStream_t on, const uint8_t *img, uint8_t *score, unsigned w, unsigned h, unsigned n,
                        unsigned threshold, unsigned long long *nz = nullptr, size_t nz_frame_words = 0) {
   const size_t fb = (size_t)w * h;
@@ -57,7 +57,7 @@ bool launch_fast_score(hipStream_t on, const uint8_t *img, uint8_t *score, unsig
   const unsigned tx = (w - 6 + 63) / 64, ty = (h - 6 + rows - 1) / rows;
   const unsigned long long nt = (unsigned long long)tx * ty * n;
   GS_ASSERT(nt < (1ull << 24)); /* the kernel's 32-bit strides (tile index) stay clear of 2^32: 2^24 tiles = 2^34 pixels per call */
-  const unsigned share = (g_tune[18] == 1 || !topo().eight_xcds()) ? 0u : (unsigned)((nt + 7) / 8); /* key 18 = 1: tiles in launch order */
+  const unsigned share = (g_tune[GSH_TUNE_STRIP_XCD] == 1 || !topo().eight_xcds()) ? 0u : (unsigned)((nt + 7) / 8); /* key 18 = 1: tiles in launch order */
   const dim3 grid(share ? share * 8u : (unsigned)nt), block(64, 4);
   const auto magic = [](unsigned d) { return d <= 1u ? 0xffffffffu : (unsigned)((1ull << 32) / d); }; /* floor(2^32 / d) */
   GS_LAUNCH(k_fast_score_q4<rows>, grid, block, 0, on, img, score, w, h, fb, threshold, tx, ty, (unsigned)nt, share, nz, nz_frame_words,
@@ -73,9 +73,9 @@ void launch_fast(const uint8_t *img, uint8_t *score, unsigned w, unsigned h, uns
   hipStream_t st = ctx().s();
   if (n == 0) return;
   if (n > kMaxZ) { /* grid.y / grid.z carry the frame index: split like every other launcher */
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ)
-      launch_fast(img + (size_t)w * h * f0, score + (size_t)w * h * f0, w, h, std::min(kMaxZ, n - f0),
-                  kps + (size_t)f0 * nkps * 12, counts + f0, nkps, threshold);
+    for_frames(n, [&](unsigned f0, unsigned nn) {
+      launch_fast(img + (size_t)w * h * f0, score + (size_t)w * h * f0, w, h, nn, kps + (size_t)f0 * nkps * 12, counts + f0, nkps, threshold);
+    });
     return;
   }
   if (w < 7 || h < 7) { /* reference loops are empty for 3 <= dim < 7 */
@@ -91,7 +91,7 @@ void launch_fast(const uint8_t *img, uint8_t *score, unsigned w, unsigned h, uns
   {
     const unsigned tx = (w - 6 + 63) / 64;
     const unsigned long long nw = (unsigned long long)tx * (h - 6);
-    if (g_tune[19] != 1 && fast_score_leaves_bitmap(threshold) && nw * 64 < (1ull << 32)) {
+    if (g_tune[GSH_TUNE_FAST_NMS] != 1 && fast_score_leaves_bitmap(threshold) && nw * 64 < (1ull << 32)) {
       const unsigned nwords = (unsigned)nw, nchunks = (nwords + kChunkWords - 1) / kChunkWords;
       GS_ASSERT((unsigned long long)n * nchunks < (1ull << 32));
       unsigned long long *nz = (unsigned long long *)ctx().scratch(SL_NZ, (size_t)n * nchunks * kChunkWords * 8);
@@ -278,18 +278,19 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
   /* XCD-aware chunk mapping (k_lbp.h) once the integral image no longer fits one XCD's 4 MB L2: 1080p -3 %, 4K block
    * noise -4 %, 4K edge maps -12 % (5.76 -> 5.08 ms per frame); 720p (3.7 MB) is 1-4 % better off in dispatch order
    * (profiles/r02l_lbp_xcd.log).  Key 13: 1 = never, 2 = always. */
-  a.xcd_swizzle = g_tune[13] == 1 ? 0u : g_tune[13] == 2 ? 1u : ((a.frame_stride * 4 >= (size_t)6 << 20 && topo().eight_xcds()) ? 1u : 0u);
+  const int xcd_key = g_tune[GSH_TUNE_LBP_XCD];
+  a.xcd_swizzle = xcd_key == 1 ? 0u : xcd_key == 2 ? 1u : ((a.frame_stride * 4 >= (size_t)6 << 20 && topo().eight_xcds()) ? 1u : 0u);
   /* k_lbp_tile's tiles go out in dispatch order = the reference's scan order within a scale, whatever the table's size: a
    * tile is read once into the LDS, so the L2 mapping is worth 1 % (eighths: 1080p block noise 0.621 vs 0.628 ms), while a
    * frame that reaches max_rects stops evaluating sooner when the tiles before the cap run first -- configs[4]'s 4K edge maps
    * (4096 rectangles reached in the last scale) 3.41 -> 3.19 ms per frame; per scale, uncapped, the two mappings are equal
    * (profiles/r05j_lbp_xcd*.log; runs of 2 / 4 tiles dealt round the XCDs equal dispatch order, 8 and 16 are 1-10 % slower).
    * Key 13 = 2: eighths for the tiles too. */
-  const unsigned tile_map = g_tune[13] == 2 ? 1u : 0u;
+  const unsigned tile_map = xcd_key == 2 ? 1u : 0u;
   const size_t lds = (size_t)dc->nstages * sizeof(LbpStage) +
                      (size_t)dc->nweaks * (sizeof(LbpWeak) + sizeof(LbpGeom)) + (size_t)dc->nsub * 4;
   GS_ASSERT(lds <= 60 * 1024 && "cascade tables must fit the block's LDS");
-  /* phases of the block-local survivor re-packing: g_tune[4] selects a preset */
+  /* phases of the block-local survivor re-packing: g_tune[GSH_TUNE_LBP_PHASE_PRESET] selects a preset */
   LbpPhases ph;
   {
     static const unsigned presets[8][kLbpMaxPhases] = {
@@ -302,9 +303,9 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
         {2, 6, 99, 99, 99, 99, 99, 99},
         {3, 7, 99, 99, 99, 99, 99, 99}};
     unsigned custom[kLbpMaxPhases];
-    const unsigned *pr = presets[(g_tune[4] >= 0 && g_tune[4] < 8) ? g_tune[4] : 0];
-    if (g_tune[4] >= 1000) { /* experiments: 1000 + e0 + 32 e1 + 1024 e2 + 32768 e3 (0 = no further split) */
-      unsigned v = (unsigned)g_tune[4] - 1000u;
+    const unsigned *pr = presets[(g_tune[GSH_TUNE_LBP_PHASE_PRESET] >= 0 && g_tune[GSH_TUNE_LBP_PHASE_PRESET] < 8) ? g_tune[GSH_TUNE_LBP_PHASE_PRESET] : 0];
+    if (g_tune[GSH_TUNE_LBP_PHASE_PRESET] >= 1000) { /* experiments: 1000 + e0 + 32 e1 + 1024 e2 + 32768 e3 (0 = no further split) */
+      unsigned v = (unsigned)g_tune[GSH_TUNE_LBP_PHASE_PRESET] - 1000u;
       for (unsigned i = 0; i < kLbpMaxPhases; i++, v >>= 5) custom[i] = (v & 31u) ? (v & 31u) : 99u;
       pr = custom;
     }
@@ -318,19 +319,19 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
     if (ph.n == 0) ph.n = 1, ph.end[0] = dc->nstages;
     ph.end[ph.n - 1] = dc->nstages;
     /* preset 0 (default): first re-packing point chosen per block between stages 2 and 8 (k_lbp.h) */
-    ph.adaptive_max = (g_tune[4] == 0 && dc->nstages > 2) ? 8u : 0u; /* 6 .. 15 within 1.5 % (profiles/r02l_lbp_adaptive_xcd.log) */
+    ph.adaptive_max = (g_tune[GSH_TUNE_LBP_PHASE_PRESET] == 0 && dc->nstages > 2) ? 8u : 0u; /* 6 .. 15 within 1.5 % (profiles/r02l_lbp_adaptive_xcd.log) */
     ph.adaptive_tenths = 2u;
     /* with quad-lane survivors (profiles/r03f_lbp_adaptive_quad.log, r03k_lbp_adaptive_next.log): +1 +2 +4 is best on
      * block noise (8 x 1080p 0.76 vs 0.80 ms for +1 +3 +6, 4K 3.15 vs 3.17) and within 0.5 % of the best on edge maps */
     ph.adaptive_next[0] = 1u, ph.adaptive_next[1] = 2u, ph.adaptive_next[2] = 4u;
     ph.tile_first = 1u, ph.tile_tenths = 7u;
-    if (g_tune[15] > 0) { /* experiments: first + 16 * tenths.  first = 0 (e.g. key 15 = 112) means "no dense stage": the dense loop still
+    if (g_tune[GSH_TUNE_LBP_TILE_SWITCH] > 0) { /* experiments: first + 16 * tenths.  first = 0 (e.g. key 15 = 112) means "no dense stage": the dense loop still
                            * has to run stage 0 for a wave to have survivors at all, so it is taken as 1 (results never depend on a key) */
-      ph.tile_first = std::max(1u, (unsigned)g_tune[15] & 15u), ph.tile_tenths = ((unsigned)g_tune[15] >> 4) & 15u;
+      ph.tile_first = std::max(1u, (unsigned)g_tune[GSH_TUNE_LBP_TILE_SWITCH] & 15u), ph.tile_tenths = ((unsigned)g_tune[GSH_TUNE_LBP_TILE_SWITCH] >> 4) & 15u;
     }
     GS_ASSERT(ph.tile_first >= 1u && ph.tile_first <= 15u && ph.tile_tenths <= 15u);
-    if (ph.adaptive_max && g_tune[9] > 0) { /* experiments: key 9 = max + 16 * tenths (+ 256 d1 + 4096 d2 + 65536 d3: later points) */
-      const unsigned v = (unsigned)g_tune[9];
+    if (ph.adaptive_max && g_tune[GSH_TUNE_LBP_ADAPTIVE] > 0) { /* experiments: key 9 = max + 16 * tenths (+ 256 d1 + 4096 d2 + 65536 d3: later points) */
+      const unsigned v = (unsigned)g_tune[GSH_TUNE_LBP_ADAPTIVE];
       ph.adaptive_max = v & 15u, ph.adaptive_tenths = (v >> 4) & 15u;
       if (v >> 8) ph.adaptive_next[0] = (v >> 8) & 15u, ph.adaptive_next[1] = (v >> 12) & 15u, ph.adaptive_next[2] = (v >> 16) & 15u;
     }
@@ -380,9 +381,9 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
   };
   struct Choice { int cfg; unsigned blocks; bool operator==(const Choice &o) const { return cfg == o.cfg && blocks == o.blocks; } };
   auto tile_choice = [&](const LbpScale &sc) -> Choice { /* cfg -1: k_lbp_cascade */
-    if (gc.guard || !ph.adaptive_max || g_tune[14] == 1) return Choice{-1, 0};
-    if (g_tune[14] >= 2) { /* experiments: one shape wherever its tile fits */
-      const int i = g_tune[14] - 2;
+    if (gc.guard || !ph.adaptive_max || g_tune[GSH_TUNE_LBP_KERNEL] == 1) return Choice{-1, 0};
+    if (g_tune[GSH_TUNE_LBP_KERNEL] >= 2) { /* experiments: one shape wherever its tile fits */
+      const int i = g_tune[GSH_TUNE_LBP_KERNEL] - 2;
       const unsigned b = i < kNumCfgs ? tile_blocks(cfgs[i], sc) : 0u;
       return b ? Choice{i, b} : Choice{-1, 0};
     }
@@ -409,11 +410,12 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
       unsigned mc = 0;
       for (unsigned s = s0; s < s1; s++) mc = std::max(mc, gc.scales[s].nchunks);
       const dim3 g(a.xcd_swizzle ? (mc + 7u) & ~7u : mc, s1 - s0, n);
-      if (a.evaluated) { /* counting build: the same kernel + one register that counts classifier evaluations */
-        if (gc.guard) GS_LAUNCH((k_lbp_cascade<true, true>), g, dim3(256), lds_all, st, a, ph);
-        else GS_LAUNCH((k_lbp_cascade<false, true>), g, dim3(256), lds_all, st, a, ph);
-      } else if (gc.guard) GS_LAUNCH(k_lbp_cascade<true>, g, dim3(256), lds_all, st, a, ph);
-      else GS_LAUNCH(k_lbp_cascade<false>, g, dim3(256), lds_all, st, a, ph);
+      with_const<false, true>(gc.guard, [&](auto GUARD) {
+        /* counting build: the same kernel + one register that counts classifier evaluations */
+        with_const<false, true>(a.evaluated != nullptr, [&](auto COUNT) {
+          GS_LAUNCH((k_lbp_cascade<GS_CV(GUARD), GS_CV(COUNT)>), g, dim3(256), lds_all, st, a, ph);
+        });
+      });
     } else {
       const TileCfg &c = cfgs[choice.cfg];
       unsigned mt = 0;
@@ -434,7 +436,7 @@ void launch_lbp_padded(const gsh_cascade *dc, const LbpGeomCache &gc, const unsi
     s0 = s1;
   }
 #ifdef GS_EXPERIMENT
-  if (g_tune[16] == 1) return; /* timing aid (scripts/bench_lbp_stages.py): the cascade kernels alone, no rect emission */
+  if (g_tune[GSH_TUNE_EXPERIMENT_16] == 1) return; /* timing aid (scripts/bench_lbp_stages.py): the cascade kernels alone, no rect emission */
 #endif
   run_compaction(mask, cnt, nch, n, max_rects, counts,
                  LbpEmit{gc.d_scales, (unsigned)gc.scales.size(), step, rects, max_rects});
@@ -449,13 +451,11 @@ void launch_lbp_unpadded(const gsh_cascade *dc, const unsigned *ii, unsigned iw,
   const LbpGeomCache &gc = cascade_prepare(dc, iw, ih, sf, mn, mx, step);
   hipStream_t st = ctx().s();
   const size_t fp = (size_t)iw * ih, pp = (size_t)(iw + 1) * (ih + 1);
-  for (unsigned f0 = 0; f0 < n; f0 += kLbpGroup) {
-    const unsigned nn = std::min(kLbpGroup, n - f0);
+  for_frames(n, kLbpGroup, [&](unsigned f0, unsigned nn) {
     unsigned *padded = (unsigned *)ctx().scratch(SL_PAD, pp * 4 * nn);
     launch_integral_pad(dim3((iw + 64) / 64, (ih + 4) / 4, nn), st, ii + fp * f0, iw, ih, padded);
-    launch_lbp_padded(dc, gc, padded, iw, ih, nn, rects + (size_t)f0 * max_rects * 4, counts + f0,
-                      max_rects, step);
-  }
+    launch_lbp_padded(dc, gc, padded, iw, ih, nn, rects + (size_t)f0 * max_rects * 4, counts + f0, max_rects, step);
+  });
 }
 
 /* one window on a (win_w+1) x (win_h+1) table: grid 1, block 64, lane 0 decides */
@@ -735,8 +735,7 @@ void launch_match_batch(const uint32_t *k1, unsigned cap1, const unsigned *n1, u
   const unsigned per1 = nset1 == 1 ? 0u : 1u, per2 = nset2 == 1 ? 0u : 1u;
   const size_t mask_b = (size_t)nchunks * kChunkWords * 8, per_pair = mask_b + (size_t)nchunks * 8 + (size_t)cap1 * 8;
   const unsigned group = (unsigned)std::min<size_t>(kMaxZ, std::max<size_t>(1, kMatchScratch / per_pair));
-  for (unsigned f0 = 0; f0 < n; f0 += group) {
-    const unsigned nn = std::min(group, n - f0);
+  for_frames(n, group, [&](unsigned f0, unsigned nn) {
     unsigned long long *mask = (unsigned long long *)ctx().scratch(SL_MASK, (size_t)nn * mask_b);
     unsigned *cnt = (unsigned *)ctx().scratch(SL_CNT, (size_t)nn * nchunks * 4);
     unsigned *best = (unsigned *)ctx().scratch(SL_BEST, (size_t)nn * cap1 * 8);
@@ -749,7 +748,7 @@ void launch_match_batch(const uint32_t *k1, unsigned cap1, const unsigned *n1, u
               dist, mask, cnt, nchunks);
     run_compaction(mask, cnt, nchunks, nn, max_matches, counts + f0,
                    MatchBatchEmit{best, dist, cap1, matches + (size_t)f0 * max_matches * 3u, max_matches});
-  }
+  });
 }
 
 }  // namespace
@@ -870,11 +869,10 @@ void gsh_orb_extract_batch(const uint8_t *img_dev, unsigned w, unsigned h, unsig
                            unsigned nkps, unsigned threshold) {
   GS_ASSERT(img_dev && scoremap_dev && kps_host && counts_host && nkps > 0 && w > 0 && h > 0);
   constexpr unsigned kOrbGroup = 4096; /* frames per pass: bounds the host-side buffers and grid.y */
-  for (unsigned f0 = 0; f0 < n; f0 += kOrbGroup) {
-    OrbJob q{img_dev + (size_t)w * h * f0, w, h, std::min(kOrbGroup, n - f0), scoremap_dev + (size_t)w * h * f0,
-             kps_host + (size_t)f0 * nkps, counts_host + f0, nkps, 0u};
+  for_frames(n, kOrbGroup, [&](unsigned f0, unsigned nn) {
+    OrbJob q{img_dev + (size_t)w * h * f0, w, h, nn, scoremap_dev + (size_t)w * h * f0, kps_host + (size_t)f0 * nkps, counts_host + f0, nkps, 0u};
     orb_extract_libm(&q, 1, threshold);
-  }
+  });
 }
 
 /* gs_orb_extract (ref :651-669) for n frames, everything on the device, no host round trip: FAST ->
@@ -894,8 +892,7 @@ void gsh_orb_extract_batch_nostdlib(const uint8_t *img_dev, unsigned w, unsigned
   }
   const size_t fb = (size_t)w * h;
   const unsigned cap = std::min(nkps * 4u, 5000u);
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     unsigned *cand = (unsigned *)ctx().scratch(SL_KPS, (size_t)nn * cap * 48 + 16);
     unsigned *cnt = (unsigned *)ctx().scratch(SL_TOT, (size_t)nn * 4 + 16);
     launch_fast(img_dev + fb * f0, scoremap_dev + fb * f0, w, h, nn, cand, cnt, cap, threshold);
@@ -904,7 +901,7 @@ void gsh_orb_extract_batch_nostdlib(const uint8_t *img_dev, unsigned w, unsigned
               out, counts_dev + f0);
     GS_LAUNCH(k_orb_describe, dim3(nkps, nn), dim3(256), 0, st, img_dev + fb * f0, w, h, fb, out,
               (const unsigned *)(counts_dev + f0), nkps);
-  }
+  });
 }
 
 size_t gsh_orb_pyramid_buffer_bytes(unsigned w, unsigned h, unsigned n_levels) {
@@ -1000,8 +997,7 @@ void gsh_orb_extract_pyramid_batch_nostdlib(const uint8_t *img_dev, unsigned w, 
   for (unsigned l = 1; l < L; l++) lev[l] = buffer_dev + off, off += fb[l] * n;
   for (unsigned l = 0; l < L; l++) sm[l] = buffer_dev + off, off += fb[l] * n;
   const unsigned per = nkps / L, cap_last = std::min(nkps * 4u, 5000u);
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     unsigned *cand = (unsigned *)ctx().scratch(SL_KPS, (size_t)nn * cap_last * 48 + 16); /* the last level's: the largest */
     unsigned *cnt = (unsigned *)ctx().scratch(SL_TOT, (size_t)nn * 4 + 16);
     unsigned *lc = level_counts_dev ? level_counts_dev + 4 * (size_t)f0 : (unsigned *)ctx().scratch(SL_ORB_LEVELS, (size_t)nn * 16);
@@ -1018,7 +1014,7 @@ void gsh_orb_extract_pyramid_batch_nostdlib(const uint8_t *img_dev, unsigned w, 
       GS_LAUNCH(k_orb_describe_level, dim3(quota, nn), dim3(256), 0, st, lev[l] + fb[l] * f0, lw[l], lh[l], fb[l], out,
                 (const unsigned *)lc, nkps, l);
     }
-  }
+  });
 }
 void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct gs_keypoint *k2,
                        unsigned n2, struct gs_match *matches, unsigned *count,
@@ -1084,17 +1080,11 @@ unsigned gs_lbp_detect(const struct gs_lbp_cascade *c, const unsigned *ii, unsig
   if (max_rects == 0) return 0;
   gsh_cascade *dc = cached_cascade(c);
   const size_t np = (size_t)iw * ih;
-  const unsigned *dii = (const unsigned *)stage_in(ii, np * 4, SL_II);
-  const bool rhost = !is_dev(rects);
-  unsigned *dr = rhost ? (unsigned *)ctx().scratch(SL_OUT, (size_t)max_rects * 16) : (unsigned *)rects;
+  const unsigned *dii = stage_in(ii, np * 4, SL_II);
+  const Staged<unsigned> dr((unsigned *)rects, (size_t)max_rects * 16, SL_OUT);
   unsigned *dcnt = (unsigned *)ctx().scratch(SL_TOT, 16);
-  launch_lbp_unpadded(dc, dii, iw, ih, 1, dr, dcnt, max_rects, scale_factor, min_scale, max_scale,
-                      step);
-  unsigned n = 0;
-  GS_HIP(hipMemcpyAsync(&n, dcnt, 4, hipMemcpyDeviceToHost, ctx().s()));
-  ctx().sync();
-  if (rhost && n) GS_HIP(hipMemcpy(rects, dr, (size_t)n * 16, hipMemcpyDeviceToHost));
-  return n;
+  launch_lbp_unpadded(dc, dii, iw, ih, 1, dr.dev, dcnt, max_rects, scale_factor, min_scale, max_scale, step);
+  return fetch_counted(dcnt, dr, 16);
 }
 
 unsigned gs_lbp_window(const struct gs_lbp_cascade *c, const unsigned *ii, unsigned iw, unsigned ih,
@@ -1153,7 +1143,7 @@ unsigned gs_fast(struct gs_image img, struct gs_image scoremap, struct gs_keypoi
    * between the two passes; the overlap is copied back. */
   if (!GS_VALID(scoremap)) return 0; /* every gs_get(scoremap) is 0: the NMS pass skips every pixel */
   const size_t nb = (size_t)w * h;
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, nb, SL_IN);
+  const uint8_t *s = stage_in(img.data, nb, SL_IN);
   const bool same = scoremap.w == w && scoremap.h == h;
   const bool mhost = !is_dev(scoremap.data);
   const unsigned ow = std::min(w, scoremap.w), oh = std::min(h, scoremap.h); /* overlap */
@@ -1166,21 +1156,16 @@ unsigned gs_fast(struct gs_image img, struct gs_image scoremap, struct gs_keypoi
     GS_HIP(hipMemcpy2DAsync(dm, w, scoremap.data, scoremap.w, ow, oh,
                             mhost ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx().s()));
   }
-  const bool khost = !is_dev(kps);
-  unsigned *dk = khost ? (unsigned *)ctx().scratch(SL_KPS, (size_t)nkps * 48) : (unsigned *)kps;
+  const Staged<unsigned> dk((unsigned *)kps, (size_t)nkps * 48, SL_KPS);
   unsigned *dcnt = (unsigned *)ctx().scratch(SL_TOT, 16);
-  launch_fast(s, dm, w, h, 1, dk, dcnt, nkps, threshold, same ? 0u : scoremap.w, same ? 0u : scoremap.h);
-  unsigned n = 0;
-  GS_HIP(hipMemcpyAsync(&n, dcnt, 4, hipMemcpyDeviceToHost, ctx().s()));
+  launch_fast(s, dm, w, h, 1, dk.dev, dcnt, nkps, threshold, same ? 0u : scoremap.w, same ? 0u : scoremap.h);
   if (same) {
     if (mhost) GS_HIP(hipMemcpyAsync(scoremap.data, dm, nb, hipMemcpyDeviceToHost, ctx().s()));
   } else {
     GS_HIP(hipMemcpy2DAsync(scoremap.data, scoremap.w, dm, w, ow, oh,
                             mhost ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx().s()));
   }
-  ctx().sync();
-  if (khost && n) GS_HIP(hipMemcpy(kps, dk, (size_t)n * 48, hipMemcpyDeviceToHost));
-  return n;
+  return fetch_counted(dcnt, dk, 48);
 }
 
 /* image patch [x-r, x+r] x [y-r, y+r] zero-filled outside the image, on the device */
@@ -1286,20 +1271,13 @@ unsigned gs_orb_extract_nostdlib(struct gs_image img, struct gs_keypoint *kps, u
   const unsigned w = img.w, h = img.h;
   if (w < 7 || h < 7) return 0;
   const size_t nb = (size_t)w * h;
-  hipStream_t st = ctx().s();
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, nb, SL_IN);
-  const bool mhost = !is_dev(scoremap_buffer), khost = !is_dev(kps);
-  uint8_t *dm = mhost ? (uint8_t *)ctx().scratch(SL_AUX, nb) : scoremap_buffer;
-  if (mhost) GS_HIP(hipMemcpyAsync(dm, scoremap_buffer, nb, hipMemcpyHostToDevice, st));
-  gs_keypoint *dk = khost ? (gs_keypoint *)ctx().scratch(SL_DESC, (size_t)nkps * sizeof(gs_keypoint)) : kps;
+  const uint8_t *s = stage_in(img.data, nb, SL_IN);
+  const Staged<uint8_t> dm(scoremap_buffer, nb, SL_AUX, /*copy_in=*/true);
+  const Staged<gs_keypoint> dk(kps, (size_t)nkps * sizeof(gs_keypoint), SL_DESC);
   unsigned *dcnt = (unsigned *)ctx().scratch(SL_KIN, 16); /* slots the batch entry below does not touch */
-  gsh_orb_extract_batch_nostdlib(s, w, h, 1, dm, dk, dcnt, nkps, threshold);
-  unsigned n = 0;
-  GS_HIP(hipMemcpyAsync(&n, dcnt, 4, hipMemcpyDeviceToHost, st));
-  if (mhost) GS_HIP(hipMemcpyAsync(scoremap_buffer, dm, nb, hipMemcpyDeviceToHost, st));
-  ctx().sync();
-  if (khost && n) GS_HIP(hipMemcpy(kps, dk, (size_t)n * sizeof(gs_keypoint), hipMemcpyDeviceToHost));
-  return n;
+  gsh_orb_extract_batch_nostdlib(s, w, h, 1, dm.dev, dk.dev, dcnt, nkps, threshold);
+  dm.back();
+  return fetch_counted(dcnt, dk, sizeof(gs_keypoint));
 }
 
 unsigned gs_orb_extract(struct gs_image img, struct gs_keypoint *kps, unsigned nkps,
@@ -1308,10 +1286,8 @@ unsigned gs_orb_extract(struct gs_image img, struct gs_keypoint *kps, unsigned n
   const unsigned w = img.w, h = img.h;
   if (w < 7 || h < 7) return 0;
   const size_t nb = (size_t)w * h;
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, nb, SL_IN);
-  const bool mhost = !is_dev(scoremap_buffer);
-  uint8_t *dm = mhost ? (uint8_t *)ctx().scratch(SL_AUX, nb) : scoremap_buffer;
-  if (mhost) GS_HIP(hipMemcpyAsync(dm, scoremap_buffer, nb, hipMemcpyHostToDevice, ctx().s()));
+  const uint8_t *s = stage_in(img.data, nb, SL_IN);
+  const Staged<uint8_t> dm(scoremap_buffer, nb, SL_AUX, /*copy_in=*/true);
   const bool khost = !is_dev(kps);
   std::vector<gs_keypoint> tmp;
   gs_keypoint *out = kps;
@@ -1319,10 +1295,10 @@ unsigned gs_orb_extract(struct gs_image img, struct gs_keypoint *kps, unsigned n
     tmp.resize(nkps);
     out = tmp.data();
   }
-  OrbLevel L{s, w, h, dm, out, nkps, 0};
+  OrbLevel L{s, w, h, dm.dev, out, nkps, 0};
   orb_extract_levels(&L, 1, threshold);
   const unsigned n = L.got;
-  if (mhost) GS_HIP(hipMemcpyAsync(scoremap_buffer, dm, nb, hipMemcpyDeviceToHost, ctx().s()));
+  dm.back();
   ctx().sync();
   if (!khost && n) gsh_upload(kps, out, (size_t)n * sizeof(gs_keypoint));
   return n;
@@ -1336,15 +1312,10 @@ unsigned gs_match_orb(const struct gs_keypoint *kps1, unsigned n1, const struct 
   const uint32_t *d1 = (const uint32_t *)stage_in(kps1, (size_t)n1 * 48, SL_IN);
   const uint32_t *d2 = n2 ? (const uint32_t *)stage_in(kps2, (size_t)n2 * 48, SL_AUX)
                           : (const uint32_t *)ctx().scratch(SL_AUX, 48);
-  const bool mhost = !is_dev(matches);
-  unsigned *dm = mhost ? (unsigned *)ctx().scratch(SL_OUT, (size_t)max_matches * 12) : (unsigned *)matches;
+  const Staged<unsigned> dm((unsigned *)matches, (size_t)max_matches * 12, SL_OUT);
   unsigned *dcnt = (unsigned *)ctx().scratch(SL_TOT, 16);
-  launch_match(d1, n1, d2, n2, dm, dcnt, max_matches, max_distance);
-  unsigned n = 0;
-  GS_HIP(hipMemcpyAsync(&n, dcnt, 4, hipMemcpyDeviceToHost, ctx().s()));
-  ctx().sync();
-  if (mhost && n) GS_HIP(hipMemcpy(matches, dm, (size_t)n * 12, hipMemcpyDeviceToHost));
-  return n;
+  launch_match(d1, n1, d2, n2, dm.dev, dcnt, max_matches, max_distance);
+  return fetch_counted(dcnt, dm, 12);
 }
 
 }  /* extern "C" */

@@ -33,6 +33,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 
@@ -315,15 +316,60 @@ inline bool is_dev(const void *p) {
 }
 
 /* host buffer -> device scratch (or pass a device pointer through) */
-inline const void *stage_in(const void *p, size_t bytes, int slot) {
+template <class T> inline const T *stage_in(const T *p, size_t bytes, int slot) {
   if (is_dev(p)) return p;
-  void *d = ctx().scratch(slot, bytes);
+  T *d = (T *)ctx().scratch(slot, bytes);
   GS_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx().s()));
   return d;
 }
 inline void finish(bool any_host_output) {
   if (any_host_output || !ctx().async) ctx().sync();
 }
+/* An output (or in-out buffer) of a drop-in entry that may be host memory: `dev` is what the launcher gets -- the caller's
+ * own pointer when it is device memory, else scratch `slot`, filled from the caller's bytes first if copy_in (gs_threshold,
+ * the score maps, `visited`).  back() queues the copy to the caller, whole or the first `prefix` bytes; a no-op for device
+ * memory.  Neither synchronises: the entry ends with finish(out.host) or its own ctx().sync(). */
+template <class T> struct Staged {
+  T *user, *dev;
+  size_t bytes;
+  bool host;
+  Staged(T *p, size_t nbytes, int slot, bool copy_in = false) : user(p), dev(p), bytes(nbytes), host(!is_dev(p)) {
+    if (!host) return;
+    dev = (T *)ctx().scratch(slot, bytes);
+    if (copy_in) GS_HIP(hipMemcpyAsync(dev, user, bytes, hipMemcpyHostToDevice, ctx().s()));
+  }
+  void back() const { back(bytes); }
+  void back(size_t prefix) const {
+    if (host) GS_HIP(hipMemcpyAsync(user, dev, prefix, hipMemcpyDeviceToHost, ctx().s()));
+  }
+  void done() const { back(), finish(host); } /* the entry's last statement when this is its only host-visible result */
+};
+/* the entries that read one image and write another in full: run(dst_dev, src_dev) between the two stagings */
+template <class Run> inline void image_to_image(struct gs_image dst, struct gs_image src, Run &&run) {
+  const uint8_t *s = stage_in(src.data, (size_t)src.w * src.h, SL_IN);
+  const Staged<uint8_t> d(dst.data, (size_t)dst.w * dst.h, SL_OUT);
+  run(d.dev, s);
+  d.done();
+}
+/* the count-returning entries: read the device count, synchronise, then bring that many records of `rec` bytes back to a
+ * host output (a blocking copy: the stream is idle) */
+template <class T> inline unsigned fetch_counted(const unsigned *count_dev, const Staged<T> &out, size_t rec) {
+  unsigned n = 0;
+  GS_HIP(hipMemcpyAsync(&n, count_dev, 4, hipMemcpyDeviceToHost, ctx().s()));
+  ctx().sync();
+  if (out.host && n) GS_HIP(hipMemcpy(out.user, out.dev, (size_t)n * rec, hipMemcpyDeviceToHost));
+  return n;
+}
+
+/* with_const<0, 1, 2>(v, [&](auto V) { ... k<GS_CV(V)> ... }): a run-time value as a template argument.  The generic lambda
+ * is called with the std::integral_constant of the listed value that equals v; a value outside the list aborts.  Every
+ * listed value instantiates the lambda's body: where only some combinations of a nested dispatch may be compiled, guard
+ * the launch with `if constexpr` on the innermost lambda's own parameter. */
+template <auto... Vs, class T, class F> inline void with_const(T v, F &&f) {
+  const bool listed = ((v == (T)Vs ? (f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+  GS_ASSERT(listed);
+}
+#define GS_CV(c) (decltype(c)::value)
 inline dim3 grid2d(unsigned w, unsigned h, unsigned n) { return dim3((w + 63) / 64, (h + 3) / 4, n); }
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -385,8 +431,17 @@ inline bool strip_ok16(unsigned w, unsigned h, const void *a, const void *b) {
  * launch runs and is bit-exact (docs/design/oracle_and_parity.md, "Shape frontier").  The split of the frames stays as it
  * is, at the documented limit: nothing was measured that would pay for depending on what one runtime version tolerates.
  * gsh_tune key 8 lowers it so that the splitting logic of every launcher can be exercised with a handful of frames */
-inline unsigned max_frames_per_launch() { return g_tune[8] > 0 ? (unsigned)g_tune[8] : 32768u; }
+inline unsigned max_frames_per_launch() {
+  return g_tune[GSH_TUNE_FRAMES_PER_LAUNCH] > 0 ? (unsigned)g_tune[GSH_TUNE_FRAMES_PER_LAUNCH] : 32768u;
+}
 #define kMaxZ (max_frames_per_launch())
+/* The frame split of every launcher: f(f0, nn) for each launch's frames [f0, f0 + nn), at most kMaxZ of them (read once per
+ * call).  With a step of the caller's own (a scratch budget, a chunk) and, for a split inside a chunk, a first frame. */
+template <class F> inline void for_frames(unsigned first, unsigned n, unsigned step, F &&f) {
+  for (unsigned f0 = first, end = first + n; f0 < end; f0 += step) f(f0, std::min(step, end - f0));
+}
+template <class F> inline void for_frames(unsigned n, unsigned step, F &&f) { for_frames(0u, n, step, f); }
+template <class F> inline void for_frames(unsigned n, F &&f) { for_frames(0u, n, kMaxZ, f); }
 
 /* the levels of the ORB pyramid driver (ref examples/nanomagick/nanomagick.c:247-260): n_levels clamped to 4, halved
  * (floor) per level, stopping before a level narrower or lower than 32.  -> L, with lw / lh [0, L) filled */

@@ -35,8 +35,8 @@ StripCfg strip_cfg(unsigned w, unsigned rows, unsigned n, unsigned waves_per_sim
   const unsigned strips = (w + 15) / 16 + (rg == 2 ? strip_realign_shift(w) + strip_realign_helper(w) : rg == 1 ? strip_ragged_shift(w) : (w & 15u) ? 1u : 0u);
   const unsigned long long waves_x = (strips + 63) / 64;
   unsigned long long t;
-  if (g_tune[0] > 0) {
-    t = (unsigned long long)g_tune[0];
+  if (g_tune[GSH_TUNE_STRIP_BAND_ROWS] > 0) {
+    t = (unsigned long long)g_tune[GSH_TUNE_STRIP_BAND_ROWS];
   } else if (waves_per_simd >= 5) {
     /* round 3, with the XCD-aware band mapping (a band's halo rows were just fetched by its own XCD) even shorter bands
      * pay: gs_sobel 6 rows (4096^2 0.706 -> 0.720 of the peak, 512 x 4K 0.705 -> 0.722; odd heights break its 2-row
@@ -73,15 +73,15 @@ StripCfg strip_cfg(unsigned w, unsigned rows, unsigned n, unsigned waves_per_sim
    * a 1920-px row kept two of a 256 x 1 block's four waves busy computing on zero fill (8 x 1080p gs_sobel at 0.21
    * of the HBM peak).  Key 1: 1 / 2 / 3 force 64 x 4 / 128 x 2 / 256 x 1, 0 = by width. */
   unsigned bx = 256, by = 1;
-  if (g_tune[1] == 1 || (g_tune[1] == 0 && strips <= 64)) bx = 64, by = 4;
-  else if (g_tune[1] == 2 || (g_tune[1] == 0 && strips <= 128)) bx = 128, by = 2;
+  if (g_tune[GSH_TUNE_STRIP_BLOCK_SHAPE] == 1 || (g_tune[GSH_TUNE_STRIP_BLOCK_SHAPE] == 0 && strips <= 64)) bx = 64, by = 4;
+  else if (g_tune[GSH_TUNE_STRIP_BLOCK_SHAPE] == 2 || (g_tune[GSH_TUNE_STRIP_BLOCK_SHAPE] == 0 && strips <= 128)) bx = 128, by = 2;
   c.block = dim3(bx, by);
   c.grid = dim3((strips + bx - 1) / bx, (nb + by - 1) / by, n);
   /* XCD-aware band mapping for the short-band (HBM-bound) kernels: one block per band row (w <= 4096), the band
    * count padded to a multiple of 8 (blocks past the last band return at once).  Key 18: 1 = off, 2 = always. */
   /* measured (profiles/r03g_strip_xcd_bands.log): 512 x 4K gs_blur(2) +3.1 %, gs_erode +2.6 %, gs_sobel +2.0 %,
    * 64 x 4096^2 copy +2 %, sobel -1 % (noise); gs_filter (waves_per_simd 6) -3.5 %: not for that one */
-  const bool want = g_tune[18] == 2 || (g_tune[18] == 0 && waves_per_simd == 5 && nb >= 64 && topo().eight_xcds());
+  const bool want = g_tune[GSH_TUNE_STRIP_XCD] == 2 || (g_tune[GSH_TUNE_STRIP_XCD] == 0 && waves_per_simd == 5 && nb >= 64 && topo().eight_xcds());
   if (want && c.grid.x == 1 && by == 1) {
     c.grid.y = (nb + 7u) & ~7u;
     c.xcd_flag = kStripXcdFlag;
@@ -95,29 +95,25 @@ StripCfg strip_cfg(unsigned w, unsigned rows, unsigned n, unsigned waves_per_sim
 void launch_sobel(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n, bool keep_cols) {
   if (w < 3 || h < 3 || n == 0) return;
 #ifdef GS_EXPERIMENT
-  if (g_tune[22] == 1) keep_cols = false; /* probe: without the dst column reads (columns 0 / w-1 then receive junk) */
+  if (g_tune[GSH_TUNE_EXPERIMENT_22] == 1) keep_cols = false; /* probe: without the dst column reads (columns 0 / w-1 then receive junk) */
 #endif
   hipStream_t st = ctx().s();
   const size_t fb = (size_t)w * h;
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     uint8_t *d = dst + fb * f0;
     const uint8_t *s = src + fb * f0;
-    if (strip_ok(w, h)) {
-      const int rg = strip_mode(w, s);
-      const StripCfg c = strip_cfg(w, h - 2, nn, 5, 2, 6, rg);
-      if (rg == 1) {
-        if (keep_cols) GS_LAUNCH((k_sobel16<true, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-        else GS_LAUNCH((k_sobel16<false, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      } else if (rg == 2) {
-        if (keep_cols) GS_LAUNCH((k_sobel16<true, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-        else GS_LAUNCH((k_sobel16<false, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      } else if (keep_cols) GS_LAUNCH(k_sobel16<true>, c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      else GS_LAUNCH(k_sobel16<false>, c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-    } else {
+    if (!strip_ok(w, h)) {
       GS_LAUNCH(k_sobel_px, grid2d(w, h, nn), dim3(64, 4), 0, st, d, s, w, h, fb);
+      return;
     }
-  }
+    const int rg = strip_mode(w, s);
+    const StripCfg c = strip_cfg(w, h - 2, nn, 5, 2, 6, rg);
+    with_const<false, true>(keep_cols, [&](auto KEEP) {
+      with_const<0, 1, 2>(rg, [&](auto RG) {
+        GS_LAUNCH((k_sobel16<GS_CV(KEEP), GS_CV(RG)>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+      });
+    });
+  });
 }
 
 template <bool DILATE>
@@ -125,20 +121,19 @@ void launch_morph(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsi
   if (n == 0) return;
   hipStream_t st = ctx().s();
   const size_t fb = (size_t)w * h;
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     uint8_t *d = dst + fb * f0;
     const uint8_t *s = src + fb * f0;
-    if (strip_ok(w, h)) {
-      const int rg = strip_mode(w, s);
-      const StripCfg c = strip_cfg(w, h, nn, 5, 2, 4, rg);
-      if (rg == 1) GS_LAUNCH((k_morph16<DILATE, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      else if (rg == 2) GS_LAUNCH((k_morph16<DILATE, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      else GS_LAUNCH(k_morph16<DILATE>, c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-    } else {
+    if (!strip_ok(w, h)) {
       GS_LAUNCH(k_morph_px<DILATE>, grid2d(w, h, nn), dim3(64, 4), 0, st, d, s, w, h, fb);
+      return;
     }
-  }
+    const int rg = strip_mode(w, s);
+    const StripCfg c = strip_cfg(w, h, nn, 5, 2, 4, rg);
+    with_const<0, 1, 2>(rg, [&](auto RG) {
+      GS_LAUNCH((k_morph16<DILATE, GS_CV(RG)>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+    });
+  });
 }
 
 /* one pass of radius K = 2..4 (k_morphk.h) over frames that pass strip_ok; the band height of the short-band route is
@@ -148,16 +143,15 @@ template <bool DILATE, int K>
 void launch_morphk(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n) {
   hipStream_t st = ctx().s();
   const size_t fb = (size_t)w * h;
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     uint8_t *d = dst + fb * f0;
     const uint8_t *s = src + fb * f0;
     const int rg = strip_mode(w, s);
     const StripCfg c = strip_cfg(w, h, nn, 5, 2 * K, kMorphkBandRows[K], rg);
-    if (rg == 1) GS_LAUNCH((k_morphk16<DILATE, K, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-    else if (rg == 2) GS_LAUNCH((k_morphk16<DILATE, K, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-    else GS_LAUNCH((k_morphk16<DILATE, K, 0>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-  }
+    with_const<0, 1, 2>(rg, [&](auto RG) {
+      GS_LAUNCH((k_morphk16<DILATE, K, GS_CV(RG)>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+    });
+  });
 }
 /* `iterations` applications of the 3x3 operator as ceil(iterations / 4) passes: radius 4 while it fits, then the remainder
  * 1..3 (1 is launch_morph).  The planes alternate so that the last pass writes dst and src is only read:
@@ -169,9 +163,9 @@ void launch_morph_iter(uint8_t *dst, const uint8_t *src, uint8_t *tmp, unsigned 
   const size_t fb = (size_t)w * h;
   if (!strip_ok(w, h)) {
     if (iterations == 1) return launch_morph<DILATE>(dst, src, w, h, n);
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ)
-      GS_LAUNCH(k_morphr_px<DILATE>, grid2d(w, h, std::min(kMaxZ, n - f0)), dim3(64, 4), 0, ctx().s(), dst + fb * f0, src + fb * f0, w, h,
-                fb, iterations);
+    for_frames(n, [&](unsigned f0, unsigned nn) {
+      GS_LAUNCH(k_morphr_px<DILATE>, grid2d(w, h, nn), dim3(64, 4), 0, ctx().s(), dst + fb * f0, src + fb * f0, w, h, fb, iterations);
+    });
     return;
   }
   const unsigned passes = (iterations + 3u) / 4u;
@@ -180,14 +174,20 @@ void launch_morph_iter(uint8_t *dst, const uint8_t *src, uint8_t *tmp, unsigned 
   for (unsigned p = 0, left = iterations; p < passes; p++) {
     const unsigned k = left >= 4u ? 4u : left;
     uint8_t *to = ((passes - p) & 1u) ? dst : tmp; /* the last pass (passes - p == 1) writes dst */
-    if (k == 4) launch_morphk<DILATE, 4>(to, from, w, h, n);
-    else if (k == 3) launch_morphk<DILATE, 3>(to, from, w, h, n);
-    else if (k == 2) launch_morphk<DILATE, 2>(to, from, w, h, n);
-    else launch_morph<DILATE>(to, from, w, h, n);
+    if (k == 1) launch_morph<DILATE>(to, from, w, h, n);
+    else with_const<2, 3, 4>(k, [&](auto K) { launch_morphk<DILATE, GS_CV(K)>(to, from, w, h, n); });
     from = to, left -= k;
   }
 }
 
+/* which table launch_integral builds, and the k_integral_wave variants that are compiled: 18.  The squares table, streaming
+ * loads and wide frames exist at 16 tiles only (the Makefile notes what this kernel already costs hipcc's register
+ * allocator). */
+enum Table { PLAIN = 0, SQUARES = 1, STREAM = 2 };
+template <unsigned TILES, bool RAGGED, bool WIDE, Table TAB> struct IntegralWaveVariant {
+  static constexpr bool compiled = TILES == 16u || (TAB == PLAIN && !WIDE);
+  static constexpr auto fn() { return k_integral_wave<(int)TILES, RAGGED, WIDE, TAB == SQUARES, TAB == STREAM>; } /* instantiated where called */
+};
 /* sq: the table of (p - 128)^2 (gs_match_template); only the banded form builds it -- false is returned, and nothing launched,
  * when this geometry would take the rows + columns form */
 bool launch_integral(const uint8_t *src, unsigned w, unsigned h, unsigned n, unsigned *ii, bool sq) {
@@ -198,66 +198,63 @@ bool launch_integral(const uint8_t *src, unsigned w, unsigned h, unsigned n, uns
    * chunks) */
   const bool banded = fp * 4 < 0x7fffffffull && w >= 32;
   if (sq && !banded) return false;
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    if (banded) {
-      const bool wide = w > 4096;
-      /* bands per frame: ~8 blocks per CU in flight, and for narrow frames no band taller than 32 rows (48 up to 2048 px).
-       * A wave of k_integral_wave owns one band and walks it row by row; a 4K row is 16 tiles of arithmetic and 8 waves per
-       * CU keep HBM busy, a 612-px row is three, and a large batch of such frames -- 8 bands of 102 rows each -- ran at
-       * 2.5 TB/s (256 x 612x816 0.255 ms; with bands of 26 rows and 4-tile waves 0.21; profiles/r06h_integral_ab_tiles_and_band_height.log).
-       * Every band costs 12 B per column (its sums: written, scanned, read), which is why wide frames keep tall bands:
-       * 64 x 1080p with 64 bands instead of 32 measured 9 % slower. */
-      unsigned nb = std::max(1u, 8u * topo().cus / nn);
-      if (w <= 1024) nb = std::max(nb, (h + 31u) / 32u);
-      else if (w <= 2048) nb = std::max(nb, (h + 47u) / 48u);
-      nb = std::min(nb, std::max(1u, h / 8));
-      if (wide) nb = std::max(nb, (h + kIntegralWideRows - 1) / kIntegralWideRows); /* a row's carry waits in LDS */
-      const unsigned BH = (h + nb - 1) / nb;
-      nb = (h + BH - 1) / BH;
-      unsigned *cs = (unsigned *)ctx().scratch(SL_HISTP, (size_t)nn * nb * w * 4);
-      const uint8_t *s = src + fp * f0;
-      unsigned *o = ii + fp * f0;
-      /* source planes the Infinity Cache (256 MB, shared with the table being written) cannot keep between the first pass and
-       * the third: both read them with streaming loads (k_integral.h).  Same-box A/B of that policy for every batch: 16 x 4096^2
-       * (256 MiB) -7 %, 64 x 4K -4 ... -12 %, 64 x 1080p (133 MB) +-0, 8 x 1080p +22 %, 32 x 720p +23 %
-       * (profiles/r06i_integral_nt_loads.log, r06j_integral_ab.log).  The plain table of frames wider than 2048 px only --
-       * the 16-tile waves -- to keep the instantiations few. */
-      const bool nt = !sq && w > 2048 && (size_t)nn * fp >= ((size_t)192 << 20) && g_tune[6] != 8; /* key 6 = 8: default policy for every batch (A/B) */
-      /* the first pass streams at that size whatever the width (256 x 720p -4 %); from 48 MiB it cost 64 - 75 MiB batches 7-12 %:
-       * the third pass then misses the cache for its source (profiles/r06aa_integral_first_pass_nt.log) */
-      const bool nt_first = !sq && (size_t)nn * fp >= ((size_t)192 << 20) && g_tune[6] != 8;
-      if (sq) GS_LAUNCH(k_integral_colsum<true>, dim3((w + 4095) / 4096, nb, nn), dim3(256), 0, st, s, w, h, BH, nb, cs);
-      else if (nt || nt_first) GS_LAUNCH((k_integral_colsum<false, true>), dim3((w + 4095) / 4096, nb, nn), dim3(256), 0, st, s, w, h, BH, nb, cs);
-      else GS_LAUNCH(k_integral_colsum<false>, dim3((w + 4095) / 4096, nb, nn), dim3(256), 0, st, s, w, h, BH, nb, cs);
-      GS_LAUNCH(k_integral_colbase, dim3((w + 63) / 64, nn), dim3(64, 16), 0, st, cs, w, nb);
-      const dim3 gw(1, (nb + 3) / 4, nn);
-      const bool rg = (w & 3u) != 0u;
-      if (sq) { /* 16 tiles whatever the width: four instantiations instead of six */
-        if (wide && rg) GS_LAUNCH((k_integral_wave<16, true, true, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-        else if (wide) GS_LAUNCH((k_integral_wave<16, false, true, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-        else if (rg) GS_LAUNCH((k_integral_wave<16, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-        else GS_LAUNCH((k_integral_wave<16, false, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      } else if (nt && wide && rg) GS_LAUNCH((k_integral_wave<16, true, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (nt && wide) GS_LAUNCH((k_integral_wave<16, false, true, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (nt && rg) GS_LAUNCH((k_integral_wave<16, true, false, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (nt) GS_LAUNCH((k_integral_wave<16, false, false, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (wide && rg) GS_LAUNCH((k_integral_wave<16, true, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (wide) GS_LAUNCH((k_integral_wave<16, false, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      /* tiles of 256 px per row: the smallest of 2 / 4 / 8 / 16 that spans it (a tile past the row's end still costs its wave scan) */
-      else if (w <= 512 && rg) GS_LAUNCH((k_integral_wave<2, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (w <= 512) GS_LAUNCH(k_integral_wave<2>, gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (w <= 1024 && rg) GS_LAUNCH((k_integral_wave<4, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (w <= 1024) GS_LAUNCH(k_integral_wave<4>, gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (w <= 2048 && rg) GS_LAUNCH((k_integral_wave<8, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (w <= 2048) GS_LAUNCH(k_integral_wave<8>, gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else if (rg) GS_LAUNCH((k_integral_wave<16, true>), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-      else GS_LAUNCH(k_integral_wave<16>, gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
-    } else {
+  if (!banded) {
+    for_frames(n, [&](unsigned f0, unsigned nn) {
       GS_LAUNCH(k_integral_rows, dim3(h, nn), dim3(256), 0, st, src + fp * f0, w, h, ii + fp * f0);
       GS_LAUNCH(k_integral_cols, dim3((w + 255) / 256, nn), dim3(256), 0, st, ii + fp * f0, w, h);
-    }
+    });
+    return true;
   }
+  const bool wide = w > 4096, rg = (w & 3u) != 0u;
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    /* bands per frame: ~8 blocks per CU in flight, and for narrow frames no band taller than 32 rows (48 up to 2048 px).
+     * A wave of k_integral_wave owns one band and walks it row by row; a 4K row is 16 tiles of arithmetic and 8 waves per
+     * CU keep HBM busy, a 612-px row is three, and a large batch of such frames -- 8 bands of 102 rows each -- ran at
+     * 2.5 TB/s (256 x 612x816 0.255 ms; with bands of 26 rows and 4-tile waves 0.21; profiles/r06h_integral_ab_tiles_and_band_height.log).
+     * Every band costs 12 B per column (its sums: written, scanned, read), which is why wide frames keep tall bands:
+     * 64 x 1080p with 64 bands instead of 32 measured 9 % slower. */
+    unsigned nb = std::max(1u, 8u * topo().cus / nn);
+    if (w <= 1024) nb = std::max(nb, (h + 31u) / 32u);
+    else if (w <= 2048) nb = std::max(nb, (h + 47u) / 48u);
+    nb = std::min(nb, std::max(1u, h / 8));
+    if (wide) nb = std::max(nb, (h + kIntegralWideRows - 1) / kIntegralWideRows); /* a row's carry waits in LDS */
+    const unsigned BH = (h + nb - 1) / nb;
+    nb = (h + BH - 1) / BH;
+    unsigned *cs = (unsigned *)ctx().scratch(SL_HISTP, (size_t)nn * nb * w * 4);
+    const uint8_t *s = src + fp * f0;
+    unsigned *o = ii + fp * f0;
+    /* source planes the Infinity Cache (256 MB, shared with the table being written) cannot keep between the first pass and
+     * the third: both read them with streaming loads (k_integral.h).  Same-box A/B of that policy for every batch: 16 x 4096^2
+     * (256 MiB) -7 %, 64 x 4K -4 ... -12 %, 64 x 1080p (133 MB) +-0, 8 x 1080p +22 %, 32 x 720p +23 %
+     * (profiles/r06i_integral_nt_loads.log, r06j_integral_ab.log).  The plain table of frames wider than 2048 px only --
+     * the 16-tile waves -- to keep the instantiations few. */
+    const bool beyond_cache = (size_t)nn * fp >= ((size_t)192 << 20) && g_tune[GSH_TUNE_COMPARE] != 8; /* key 6 = 8: default policy for every batch (A/B) */
+    const bool nt = !sq && w > 2048 && beyond_cache;
+    /* the first pass streams at that size whatever the width (256 x 720p -4 %); from 48 MiB it cost 64 - 75 MiB batches 7-12 %:
+     * the third pass then misses the cache for its source (profiles/r06aa_integral_first_pass_nt.log) */
+    const bool nt_first = !sq && beyond_cache;
+    /* the first pass: three variants, one per table */
+    const dim3 gc((w + 4095) / 4096, nb, nn);
+    with_const<PLAIN, SQUARES, STREAM>(sq ? SQUARES : (nt || nt_first) ? STREAM : PLAIN, [&](auto TAB) {
+      GS_LAUNCH((k_integral_colsum<GS_CV(TAB) == SQUARES, GS_CV(TAB) == STREAM>), gc, dim3(256), 0, st, s, w, h, BH, nb, cs);
+    });
+    GS_LAUNCH(k_integral_colbase, dim3((w + 63) / 64, nn), dim3(64, 16), 0, st, cs, w, nb);
+    const dim3 gw(1, (nb + 3) / 4, nn);
+    /* tiles of 256 px per row: the smallest of 2 / 4 / 8 / 16 that spans it (a tile past the row's end still costs its wave scan);
+     * the squares table 16 tiles whatever the width: four instantiations instead of six.  (nt and wide imply w > 2048.) */
+    const unsigned tiles = (sq || w > 2048) ? 16u : w <= 512 ? 2u : w <= 1024 ? 4u : 8u;
+    with_const<2u, 4u, 8u, 16u>(tiles, [&](auto TILES) {
+      with_const<false, true>(rg, [&](auto RG) {
+        with_const<false, true>(wide, [&](auto WIDE) {
+          with_const<PLAIN, SQUARES, STREAM>(sq ? SQUARES : nt ? STREAM : PLAIN, [&](auto TAB) {
+            using K = IntegralWaveVariant<GS_CV(TILES), GS_CV(RG), GS_CV(WIDE), GS_CV(TAB)>;
+            if constexpr (K::compiled) GS_LAUNCH(K::fn(), gw, dim3(256), 0, st, s, w, h, BH, nb, (const unsigned *)cs, o);
+            else GS_ASSERT(!"k_integral_wave: a combination the rule above does not produce");
+          });
+        });
+      });
+    });
+  });
   return true;
 }
 
@@ -269,12 +266,11 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
   hipStream_t st = ctx().s();
   const size_t fp = (size_t)w * h;
   const unsigned r = std::min(radius, std::max(w, h)); /* larger windows clip identically */
-  if (g_tune[6] != 3 && r >= 1 && r <= 127 && w <= 4096 && strip_ok(w, h)) {
+  if (g_tune[GSH_TUNE_COMPARE] != 3 && r >= 1 && r <= 127 && w <= 4096 && strip_ok(w, h)) {
     /* sliding box sums straight from the source rows (k_box.h): 3-4 B/px instead of the ~16 of the integral-image
      * route below (64 4K frames: 2.8 ms whatever the radius; this one: r = 16 0.36 ms, r = 40 0.63 ms); the kernel's
      * u16 column sums and LDS halo hold up to r = 127 */
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-      const unsigned nn = std::min(kMaxZ, n - f0);
+    for_frames(n, [&](unsigned f0, unsigned nn) {
       /* r <= 16: the window's raw rows stay in registers (k_box16r: 2 B/px instead of 3-4; 64 x 4K: 0.22 ms for r <= 9,
        * 0.28 up to 16, against 0.31-0.42 -- profiles/r03r_box_ring.log).  Key 6 = 4: k_box16 always. */
       /* ragged rows: the ring kernel over the whole strips (the last one only feeds its neighbour) + k_box_edge for the
@@ -282,7 +278,7 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
        * choice between two edge divisors, shifted tail loads inside the block) was no faster than the any-radius kernel --
        * 116-152 registers at r = 4..5 instead of 84-92, one wave per SIMD from r = 12
        * (profiles/r04k_box_ring_ragged_not_kept.log: 3838 x 2160 r = 5 0.446 vs 0.434 ms, r = 16 0.73 vs 0.53). */
-      const bool ring = g_tune[6] != 4 && r <= box_ring_max() && w >= 32 && h >= 2 * r + 1 &&
+      const bool ring = g_tune[GSH_TUNE_COMPARE] != 4 && r <= box_ring_max() && w >= 32 && h >= 2 * r + 1 &&
                         (MODE == 0 || (c > -(1 << 30) && c < (1 << 30)));
       /* band height: the launch should be whole rounds of the blocks the chip holds (256 CUs x 4 of them, fewer for the
        * register-heavy ring kernels of r >= 8 / 10), and a band first loads 2r+1 rows it does not output -- loads and
@@ -293,8 +289,8 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
       const unsigned threads = w <= 1024 ? 64u : w <= 2048 ? 128u : 256u; /* a thread owns 16 px of the row */
       const unsigned slots = topo().cus * box_blocks_per_cu(MODE, ring ? r : 0u, threads);
       unsigned T = h;
-      if (g_tune[0] > 0) {
-        T = (unsigned)g_tune[0];
+      if (g_tune[GSH_TUNE_STRIP_BAND_ROWS] > 0) {
+        T = (unsigned)g_tune[GSH_TUNE_STRIP_BAND_ROWS];
       } else {
         /* once the launch is several full rounds, more bands only add prologues (cost ~ nn h / slots + nn nbc k / slots
          * grows with nbc), so the search stops at 4 rounds' worth of blocks: at most 4096 candidates however tall
@@ -318,7 +314,8 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
       if (ring && ragged(w)) {
         /* about four waves per SIMD, and bands at least two windows tall (a band starts with 2 r + 1 rows of loads) */
         const unsigned want = std::max(1u, 4u * 4u * topo().cus / nn);
-        const unsigned Te = g_tune[0] > 0 ? (unsigned)g_tune[0] : std::max((h + want - 1) / want, std::min(h, 2u * (2u * r + 1u)));
+        const int band_rows = g_tune[GSH_TUNE_STRIP_BAND_ROWS];
+        const unsigned Te = band_rows > 0 ? (unsigned)band_rows : std::max((h + want - 1) / want, std::min(h, 2u * (2u * r + 1u)));
         const dim3 ge(1, (h + Te - 1) / Te, nn);
         /* The edge launch is a chain of memory latencies (15-30 us however little it computes, growing with the 2 r + 1
          * start-up rows) and touches other columns of dst than the body.  For r >= 12 on large batches it goes to the side
@@ -328,7 +325,7 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
          * Key 6 = 7: always on the side stream. */
         bool side = false;
 #ifndef GS_EMU
-        side = g_tune[6] == 7 || (r >= 12u && (size_t)nn * fp >= ((size_t)16 << 20));
+        side = g_tune[GSH_TUNE_COMPARE] == 7 || (r >= 12u && (size_t)nn * fp >= ((size_t)16 << 20));
         if (side) {
           Ctx &cx = ctx();
           cx.ensure_side();
@@ -346,17 +343,15 @@ void launch_box_generic(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h
       } else {
         launch_box(MODE, ring ? r : 0u, dim3(1, nb, nn), threads, st, dst + fp * f0, src + fp * f0, w, h, T, fp, r, c);
       }
-    }
+    });
     return;
   }
   const unsigned group = (unsigned)std::max<size_t>(1, std::min<size_t>(n, (256u << 20) / (fp * 4) + 1));
   unsigned *ii = (unsigned *)ctx().scratch(SL_II, fp * 4 * group);
-  for (unsigned f0 = 0; f0 < n; f0 += group) {
-    const unsigned nn = std::min(group, n - f0);
+  for_frames(n, group, [&](unsigned f0, unsigned nn) {
     launch_integral(src + fp * f0, w, h, nn, ii);
-    GS_LAUNCH(k_box_px<MODE>, grid2d(w, h, nn), dim3(64, 4), 0, st, dst + fp * f0, src + fp * f0,
-              (const unsigned *)ii, w, h, r, c, fp);
-  }
+    GS_LAUNCH(k_box_px<MODE>, grid2d(w, h, nn), dim3(64, 4), 0, st, dst + fp * f0, src + fp * f0, (const unsigned *)ii, w, h, r, c, fp);
+  });
 }
 
 void launch_blur(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n,
@@ -365,27 +360,19 @@ void launch_blur(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsig
   hipStream_t st = ctx().s();
   const size_t fb = (size_t)w * h;
   if (radius >= 1 && radius <= 3 && strip_ok(w, h) && h > 2 * radius && w > 2 * radius) {
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-      const unsigned nn = std::min(kMaxZ, n - f0);
+    for_frames(n, [&](unsigned f0, unsigned nn) {
       uint8_t *d = dst + fb * f0;
       const uint8_t *s = src + fb * f0;
       const int rg = strip_mode(w, s);
       const StripCfg c = strip_cfg(w, h, nn, 5, radius, radius == 1 ? 4 : radius == 2 ? 6 : 12, rg);
-      if (rg == 1) {
-        if (radius == 1) GS_LAUNCH((k_blur16<1, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-        else if (radius == 2) GS_LAUNCH((k_blur16<2, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-        else GS_LAUNCH((k_blur16<3, 1>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      } else if (rg == 2) {
-        if (radius == 1) GS_LAUNCH((k_blur16<1, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-        else if (radius == 2) GS_LAUNCH((k_blur16<2, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-        else GS_LAUNCH((k_blur16<3, 2>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      } else if (radius == 1) GS_LAUNCH(k_blur16<1>, c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      else if (radius == 2) GS_LAUNCH(k_blur16<2>, c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
-      else GS_LAUNCH(k_blur16<3>, c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+      with_const<1, 2, 3>(radius, [&](auto R) {
+        with_const<0, 1, 2>(rg, [&](auto RG) {
+          GS_LAUNCH((k_blur16<GS_CV(R), GS_CV(RG)>), c.grid, c.block, 0, st, d, s, w, h, c.T, fb | c.xcd_flag);
+        });
+      });
       /* the 2*radius vertically clipped rows of each frame get their true divisors */
-      GS_LAUNCH(k_blur_edge_rows, dim3((w + 255) / 256, 2 * radius, nn), dim3(256), 0, st, d, s, w, h,
-                (int)radius, fb);
-    }
+      GS_LAUNCH(k_blur_edge_rows, dim3((w + 255) / 256, 2 * radius, nn), dim3(256), 0, st, d, s, w, h, (int)radius, fb);
+    });
     return;
   }
   if (radius == 0) { /* 1x1 window: identity (sum/1) */
@@ -402,7 +389,7 @@ void launch_blur(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsig
  * (256 CUs x 5 resident blocks) down to 16 trips per block, at most 256 blocks per frame for k_hist_reduce. */
 constexpr unsigned kHistThreads = 256;
 unsigned hist_bpf(size_t frame_bytes, unsigned n) {
-  if (g_tune[11] > 0) return (unsigned)g_tune[11];
+  if (g_tune[GSH_TUNE_HIST_BLOCKS] > 0) return (unsigned)g_tune[GSH_TUNE_HIST_BLOCKS];
   const size_t bt = kHistThreads, trips = 64;
   const size_t chunks = frame_bytes / 16 + 1;
   const size_t by_size = (chunks + bt * trips - 1) / (bt * trips);
@@ -411,16 +398,16 @@ unsigned hist_bpf(size_t frame_bytes, unsigned n) {
 }
 void launch_hist_partial(dim3 grid, hipStream_t st, const uint8_t *img, size_t frame_bytes, unsigned *partial) {
   /* more bytes than the Infinity Cache keeps (192 MiB and up): streaming loads (k_pointwise.h) */
-  if ((size_t)grid.y * grid.z * frame_bytes >= ((size_t)192 << 20))
-    GS_LAUNCH((k_hist_partial<kHistThreads, true>), grid, dim3(kHistThreads), 0, st, img, frame_bytes, partial);
-  else GS_LAUNCH(k_hist_partial<kHistThreads>, grid, dim3(kHistThreads), 0, st, img, frame_bytes, partial);
+  with_const<false, true>((size_t)grid.y * grid.z * frame_bytes >= ((size_t)192 << 20), [&](auto NT) {
+    GS_LAUNCH((k_hist_partial<kHistThreads, GS_CV(NT)>), grid, dim3(kHistThreads), 0, st, img, frame_bytes, partial);
+  });
 }
 void launch_histogram(const uint8_t *img, size_t frame_bytes, unsigned n, unsigned *hist) {
   if (n == 0) return;
   hipStream_t st = ctx().s();
   /* k_hist_partial addresses a frame with 32-bit offsets: count a huge image in pieces (key 12: piece size in
    * bytes, so that tests reach this path with small images) */
-  const size_t piece_bytes = g_tune[12] > 0 ? (size_t)g_tune[12] : kHistMaxFrame;
+  const size_t piece_bytes = g_tune[GSH_TUNE_HIST_PIECE] > 0 ? (size_t)g_tune[GSH_TUNE_HIST_PIECE] : kHistMaxFrame;
   if (frame_bytes > piece_bytes) {
     const unsigned pieces = (unsigned)(frame_bytes / piece_bytes);
     const size_t rest = frame_bytes - (size_t)pieces * piece_bytes;
@@ -437,13 +424,11 @@ void launch_histogram(const uint8_t *img, size_t frame_bytes, unsigned n, unsign
     return;
   }
   const unsigned bpf = hist_bpf(frame_bytes, n);
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     unsigned *partial = (unsigned *)ctx().scratch(SL_HISTP, (size_t)nn * bpf * 256 * 4);
     launch_hist_partial(dim3(bpf, nn), st, img + frame_bytes * f0, frame_bytes, partial);
-    GS_LAUNCH(k_hist_reduce, dim3(nn), dim3(256), 0, st, (const unsigned *)partial, bpf,
-              hist + (size_t)f0 * 256, 0u);
-  }
+    GS_LAUNCH(k_hist_reduce, dim3(nn), dim3(256), 0, st, (const unsigned *)partial, bpf, hist + (size_t)f0 * 256, 0u);
+  });
 }
 void launch_threshold(uint8_t *img, size_t frame_bytes, unsigned n, const uint8_t *thr_dev,
                       unsigned thr_const, hipStream_t on = nullptr, int thr_off = 0) {
@@ -451,20 +436,17 @@ void launch_threshold(uint8_t *img, size_t frame_bytes, unsigned n, const uint8_
   hipStream_t st = on ? on : ctx().s();
   const size_t chunks = frame_bytes / 16 + 2;
   const unsigned bx = (unsigned)std::max<size_t>(1, std::min<size_t>((chunks + 255) / 256, 2048));
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    GS_LAUNCH(k_threshold, dim3(bx, nn), dim3(256), 0, st, img + frame_bytes * f0, frame_bytes,
-              thr_dev ? thr_dev + f0 : nullptr, thr_const, thr_off);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_threshold, dim3(bx, nn), dim3(256), 0, st, img + frame_bytes * f0, frame_bytes, thr_dev ? thr_dev + f0 : nullptr, thr_const,
+              thr_off);
+  });
 }
 void launch_otsu(const uint8_t *img, unsigned w, unsigned h, unsigned n, unsigned *hist,
                  uint8_t *thr) {
   launch_histogram(img, (size_t)(w * h), n, hist);
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    GS_LAUNCH(k_otsu, dim3(nn), dim3(256), 0, ctx().s(), hist + (size_t)f0 * 256, w * h, thr + f0,
-              (const unsigned *)nullptr, 0u, 0u);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_otsu, dim3(nn), dim3(256), 0, ctx().s(), hist + (size_t)f0 * 256, w * h, thr + f0, (const unsigned *)nullptr, 0u, 0u);
+  });
 }
 
 void synth_jump_table(SynthJump &J) {
@@ -509,8 +491,8 @@ static unsigned resize_extent(unsigned c, unsigned s, unsigned d) {
 struct ResizePlan { unsigned band, lds; };
 static ResizePlan resize_plan(unsigned dw, unsigned dh, unsigned sw, unsigned sh, bool windows) {
   ResizePlan pl = {16u, 0u};
-  const bool dense = (unsigned long long)sw * sh <= 4ull * dw * dh || g_tune[25] == 2;
-  if (g_tune[25] != 1 && (windows || dense)) {
+  const bool dense = (unsigned long long)sw * sh <= 4ull * dw * dh || g_tune[GSH_TUNE_GEOM_FORM] == 2;
+  if (g_tune[GSH_TUNE_GEOM_FORM] != 1 && (windows || dense)) {
     if (windows) {
       pl.lds = kResizeLdsSmall;
     } else {
@@ -531,28 +513,28 @@ static void launch_resize(uint8_t *dst, unsigned dw, unsigned dh, const uint8_t 
   ResizeArgs a;
   a.dst = dst, a.src = src, a.rois = rois, a.frame_of = frame_of;
   a.dw = dw, a.dh = dh, a.sw = sw, a.sh = sh, a.n = n;
-  a.band = pl.band, a.lds = pl.lds, a.any_density = g_tune[25] == 2 ? 1u : 0u;
+  a.band = pl.band, a.lds = pl.lds, a.any_density = g_tune[GSH_TUNE_GEOM_FORM] == 2 ? 1u : 0u;
   const bool nt = (unsigned long long)dw * dh * count > (256ull << 20); /* beyond the Infinity Cache: streaming stores */
   hipStream_t st = ctx().s();
-  for (unsigned f0 = 0; f0 < count; f0 += kMaxZ) {
-    const dim3 grid((dw + 255) / 256, (dh + pl.band - 1) / pl.band, std::min(kMaxZ, count - f0));
+  for_frames(count, [&](unsigned f0, unsigned nn) {
+    const dim3 grid((dw + 255) / 256, (dh + pl.band - 1) / pl.band, nn);
     a.z0 = f0;
-    if (nearest && nt) GS_LAUNCH((k_resize_tile<true, true>), grid, dim3(64, 4), pl.lds, st, a);
-    else if (nearest) GS_LAUNCH((k_resize_tile<true, false>), grid, dim3(64, 4), pl.lds, st, a);
-    else if (nt) GS_LAUNCH((k_resize_tile<false, true>), grid, dim3(64, 4), pl.lds, st, a);
-    else GS_LAUNCH((k_resize_tile<false, false>), grid, dim3(64, 4), pl.lds, st, a);
-  }
+    with_const<false, true>(nearest, [&](auto NEAREST) {
+      with_const<false, true>(nt, [&](auto NT) { GS_LAUNCH((k_resize_tile<GS_CV(NEAREST), GS_CV(NT)>), grid, dim3(64, 4), pl.lds, st, a); });
+    });
+  });
 }
 static void launch_crop(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n, struct gs_rect roi) {
   GS_ASSERT(roi.x <= sw && roi.w <= sw - roi.x && roi.y <= sh && roi.h <= sh - roi.y); /* inside the frame, no 32-bit wrap */
   const size_t sfb = (size_t)sw * sh, dfb = (size_t)roi.w * roi.h;
   const bool nt = (unsigned long long)dfb * n > (256ull << 20);
   hipStream_t st = ctx().s();
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const dim3 grid(((roi.w + 15) / 16 + 63) / 64, (roi.h + 3) / 4, std::min(kMaxZ, n - f0));
-    if (nt) GS_LAUNCH(k_crop_rows<true>, grid, dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh, roi.x, roi.y, roi.w, roi.h);
-    else GS_LAUNCH(k_crop_rows<false>, grid, dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh, roi.x, roi.y, roi.w, roi.h);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    const dim3 grid(((roi.w + 15) / 16 + 63) / 64, (roi.h + 3) / 4, nn);
+    with_const<false, true>(nt, [&](auto NT) {
+      GS_LAUNCH(k_crop_rows<GS_CV(NT)>, grid, dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh, roi.x, roi.y, roi.w, roi.h);
+    });
+  });
 }
 static bool apart(const uint8_t *a, size_t na, const uint8_t *b, size_t nb) { return a + na <= b || b + nb <= a; }
 
@@ -569,11 +551,12 @@ static TmForm tm_form(unsigned tw, unsigned th, unsigned rw, unsigned rh, unsign
   /* few 64 x 128 tiles: 32 x 64 tiles, the template rows split over the block's four waves.  The rule counts the blocks of
    * the WHOLE launch, tiles per frame times frames: a 720p frame alone has 120 whole tiles for 256 CUs, five of them fill
    * the chip.  key 20 = 8: 64 x 128 tiles, banded, whatever the size */
-  f.split = g_tune[20] == 3 || (g_tune[20] != 2 && g_tune[20] != 8 && (unsigned long long)((rw + 127) / 128) * ((rh + 63) / 64) * frames < 512);
+  const int key = g_tune[GSH_TUNE_TMATCH];
+  f.split = key == 3 || (key != 2 && key != 8 && (unsigned long long)((rw + 127) / 128) * ((rh + 63) / 64) * frames < 512);
   f.istride = (f.split ? 32 : 96) + 32 * nkc + 16;
   /* SPLIT = 1 takes templates taller than a band kTmBand rows at a time (k_tmatch.h BAND: 33 KB of LDS per block instead of 79 at
    * 128 x 128, four blocks per CU); key 20 = 2: the whole template resident, as in round 3 */
-  f.band = !f.split && g_tune[20] != 2 && th > kTmBand;
+  f.band = !f.split && key != 2 && th > kTmBand;
   const unsigned rows = f.band ? kTmBand : th;
   f.lds = std::max<size_t>((size_t)((f.split ? 31 : 63) + rows) * f.istride + (size_t)rows * (32 * nkc + 48) + 16, f.split ? 32768 : 0);
   return f;
@@ -588,7 +571,8 @@ static TmRoute tm_route(unsigned iw, unsigned ih, unsigned tw, unsigned th) {
   const size_t ib = (size_t)iw * ih, tb = (size_t)tw * th;
   const unsigned nkc = (tw + 31 + 31) / 32;
   const TmForm one = tm_form(tw, th, iw - tw + 1, ih - th + 1, 1);
-  if (g_tune[20] != 1 && tw >= 16 && nkc <= 9 && th >= 4 && (tb >= 512 || g_tune[20] == 2 || g_tune[20] == 3 || g_tune[20] == 8) && tb <= 32768 &&
+  const int key = g_tune[GSH_TUNE_TMATCH];
+  if (key != 1 && tw >= 16 && nkc <= 9 && th >= 4 && (tb >= 512 || key == 2 || key == 3 || key == 8) && tb <= 32768 &&
       one.lds <= 150 * 1024 && ib < 0x7fffffffull)
     return TM_MFMA;
   return tw <= kTmplTile - 3 ? TM_DOT : TM_PX;
@@ -604,8 +588,19 @@ static unsigned tm_chunk_frames(TmRoute route, unsigned iw, unsigned ih, unsigne
   const size_t per = route == TM_MFMA ? ((size_t)ih * (iw + 1) + (size_t)rw * rh) * 4 : locate ? (size_t)rw * rh : 0;
   size_t c = std::min<size_t>(n, kMaxZ);
   if (per) c = std::min(c, std::max<size_t>(1, kTmScratchBudget / per));
-  if (g_tune[26] > 0) c = std::min<size_t>(c, (size_t)g_tune[26]);
+  if (g_tune[GSH_TUNE_TMATCH_CHUNK] > 0) c = std::min<size_t>(c, (size_t)g_tune[GSH_TUNE_TMATCH_CHUNK]);
   return (unsigned)c;
+}
+/* THE list of the k_match_template_mfma variants, for the launch and for the attribute that lets a variant take more than
+ * 64 KB of dynamic LDS: form 0 = 64 x 128 tiles, 1 = 32 x 64 tiles with the template rows split over four waves, 2 = 64 x 128
+ * tiles, banded; one instantiation per number of K steps (k_tmatch.h): nkc = 2 .. 9 for templates 16 .. 257 wide */
+typedef void (*TmKernel)(TmArgs);
+template <class F> static void tm_variant(unsigned form, unsigned nkc, F &&f) {
+  with_const<0u, 1u, 2u>(form, [&](auto FORM) {
+    with_const<2u, 3u, 4u, 5u, 6u, 7u, 8u, 9u>(nkc, [&](auto NKC) {
+      f((TmKernel)k_match_template_mfma<GS_CV(FORM) == 1u ? 4 : 1, GS_CV(NKC), GS_CV(FORM) == 2u>);
+    });
+  });
 }
 /* nn frames (iw x ih, back to back) against one template (ntmpl == 1) or template f for frame f (ntmpl == nn) in one set of
  * launches on the current stream.  d: the nn result maps; d == nullptr (matrix-core route only): the locate epilogue, keys[f]
@@ -632,7 +627,7 @@ static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, c
      * SLOWER than the two passes of round 3 (row prefix + sliding columns), which stay for small frames, for key 20 = 4 and
      * for geometries the banded integral does not take (key 20 = 5: the table route whatever the size);
      * profiles/r04v_match_template_integral_squares.log */
-    if (g_tune[20] != 4 && (ib >= (4u << 20) || g_tune[20] == 5) && launch_integral(s, iw, ih, nn, rowp, /*sq=*/true)) {
+    if (g_tune[GSH_TUNE_TMATCH] != 4 && (ib >= (4u << 20) || g_tune[GSH_TUNE_TMATCH] == 5) && launch_integral(s, iw, ih, nn, rowp, /*sq=*/true)) {
       GS_LAUNCH(k_tm_s2_corners, dim3((rw + 255) / 256, rh, nn), dim3(256), 0, st, (const unsigned *)rowp, iw, ih, tw, th, rw, rh, s2);
     } else {
       GS_LAUNCH(k_tm_rowprefix, dim3((ih + 3) / 4, 1, nn), dim3(64, 4), 0, st, s, iw, ih, rowp);
@@ -645,31 +640,16 @@ static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, c
     static std::atomic<unsigned long long> lds_raised{0};
     const unsigned long long dev_bit = 1ull << ((unsigned)ctx().device & 63u);
     if (ctx().device >= 64 || !(lds_raised.load(std::memory_order_acquire) & dev_bit)) {
-#define GS_TM_FNS(S) (const void *)k_match_template_mfma<S, 2>, (const void *)k_match_template_mfma<S, 3>, (const void *)k_match_template_mfma<S, 4>, \
-                     (const void *)k_match_template_mfma<S, 5>, (const void *)k_match_template_mfma<S, 6>, (const void *)k_match_template_mfma<S, 7>, \
-                     (const void *)k_match_template_mfma<S, 8>, (const void *)k_match_template_mfma<S, 9>
-      const void *fns[] = {GS_TM_FNS(1), GS_TM_FNS(4),
-                           (const void *)k_match_template_mfma<1, 2, true>, (const void *)k_match_template_mfma<1, 3, true>, (const void *)k_match_template_mfma<1, 4, true>,
-                           (const void *)k_match_template_mfma<1, 5, true>, (const void *)k_match_template_mfma<1, 6, true>, (const void *)k_match_template_mfma<1, 7, true>,
-                           (const void *)k_match_template_mfma<1, 8, true>, (const void *)k_match_template_mfma<1, 9, true>};
-#undef GS_TM_FNS
-      for (const void *fn : fns) GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      for (unsigned form = 0; form < 3; form++)
+        for (unsigned k = 2; k <= 9; k++)
+          tm_variant(form, k, [](TmKernel fn) { GS_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
       lds_raised.fetch_or(dev_bit, std::memory_order_release);
     }
 #endif
     TmArgs ta{s, iw, ih, (const uint8_t *)tpad, (const unsigned *)tsqp, tw, th, s2, d, rw, rh, nkc, istride, tstride,
               ntmpl > 1 ? (unsigned)tpb : 0u, ntmpl > 1 ? 1u : 0u, keys};
-    /* one instantiation per number of K steps (k_tmatch.h): nkc = 2 .. 9 for templates 16 .. 257 wide */
-    const dim3 gs4((rw + 63) / 64, (rh + 31) / 32, nn), gs1((rw + 127) / 128, (rh + 63) / 64, nn);
-    GS_ASSERT(nkc >= 2 && nkc <= 9);
-    switch (nkc * 4 + (tm_split ? 1u : tm_band ? 2u : 0u)) {
-#define GS_TM_CASE(K)                                                                                   \
-  case K * 4: GS_LAUNCH((k_match_template_mfma<1, K>), gs1, dim3(256), tm_lds, st, ta); break;          \
-  case K * 4 + 1: GS_LAUNCH((k_match_template_mfma<4, K>), gs4, dim3(256), tm_lds, st, ta); break;      \
-  case K * 4 + 2: GS_LAUNCH((k_match_template_mfma<1, K, true>), gs1, dim3(256), tm_lds, st, ta); break;
-      GS_TM_CASE(2) GS_TM_CASE(3) GS_TM_CASE(4) GS_TM_CASE(5) GS_TM_CASE(6) GS_TM_CASE(7) GS_TM_CASE(8) GS_TM_CASE(9)
-#undef GS_TM_CASE
-    }
+    const dim3 grid = tm_split ? dim3((rw + 63) / 64, (rh + 31) / 32, nn) : dim3((rw + 127) / 128, (rh + 63) / 64, nn);
+    tm_variant(tm_split ? 1u : tm_band ? 2u : 0u, nkc, [&](TmKernel fn) { GS_LAUNCH(fn, grid, dim3(256), tm_lds, st, ta); });
     return;
   }
   GS_ASSERT(d != nullptr); /* the other routes locate through a map (tm_batch) */
@@ -693,11 +673,10 @@ static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, c
 /* best / score of n maps of rw x rh from their keys; maps == nullptr: the keys are there already */
 static void tm_argmax(const uint8_t *maps, unsigned rw, unsigned rh, unsigned n, unsigned long long *keys) {
   const unsigned long long rb = (unsigned long long)rw * rh;
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     GS_LAUNCH(k_argmax_first, dim3((unsigned)((rb + 2047) / 2048), nn), dim3(256), 0, ctx().s(), maps + (size_t)rb * f0, rb,
               (unsigned long long *)nullptr, keys + f0);
-  }
+  });
 }
 /* gsh_match_template_batch (result != nullptr) and gsh_locate_template_batch (best != nullptr) */
 static void tm_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
@@ -716,8 +695,7 @@ static void tm_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, c
     keys = (unsigned long long *)ctx().scratch(SL_BEST, (size_t)n * 8);
     GS_HIP(hipMemsetAsync(keys, 0, (size_t)n * 8, st));
   }
-  for (unsigned f0 = 0; f0 < n; f0 += chunk) {
-    const unsigned nn = std::min(chunk, n - f0);
+  for_frames(n, chunk, [&](unsigned f0, unsigned nn) {
     const uint8_t *s = img + ib * f0, *t = ntmpl > 1 ? tmpl + tb * f0 : tmpl;
     const unsigned nt = ntmpl > 1 ? nn : 1u;
     if (result) tm_launch(s, iw, ih, nn, t, tw, th, nt, result + rb * f0, nullptr);
@@ -727,7 +705,7 @@ static void tm_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, c
       tm_launch(s, iw, ih, nn, t, tw, th, nt, maps, nullptr);
       tm_argmax(maps, rw, rh, nn, keys + f0);
     }
-  }
+  });
   if (!result) GS_LAUNCH(k_best_from_keys, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, rw, (unsigned *)best, score);
 }
 
@@ -738,10 +716,11 @@ extern "C" {
 #ifdef GS_EXPERIMENT
 void gsh_probe_strip_copy(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, unsigned n) {
   GS_ASSERT(dst && src && w >= 32);
-  const StripCfg c = strip_cfg(w, h, n, 5, 2, g_tune[0] > 0 ? (unsigned)g_tune[0] : 8u, ragged(w) ? 1 : 0);
-  if (g_tune[23] == 1) GS_LAUNCH((k_strip_copy<0, true>), c.grid, c.block, 0, ctx().s(), dst, src, w, h, c.T, (size_t)w * h | c.xcd_flag);
-  else if (ragged(w)) GS_LAUNCH(k_strip_copy<1>, c.grid, c.block, 0, ctx().s(), dst, src, w, h, c.T, (size_t)w * h | c.xcd_flag);
-  else GS_LAUNCH(k_strip_copy<0>, c.grid, c.block, 0, ctx().s(), dst, src, w, h, c.T, (size_t)w * h | c.xcd_flag);
+  const StripCfg c = strip_cfg(w, h, n, 5, 2, g_tune[GSH_TUNE_STRIP_BAND_ROWS] > 0 ? (unsigned)g_tune[GSH_TUNE_STRIP_BAND_ROWS] : 8u, ragged(w) ? 1 : 0);
+  /* 2: whole strips with the stencils' halo load */
+  with_const<0, 1, 2>(g_tune[GSH_TUNE_EXPERIMENT_23] == 1 ? 2 : ragged(w) ? 1 : 0, [&](auto V) {
+    GS_LAUNCH((k_strip_copy<GS_CV(V) == 1 ? 1 : 0, GS_CV(V) == 2>), c.grid, c.block, 0, ctx().s(), dst, src, w, h, c.T, (size_t)w * h | c.xcd_flag);
+  });
 }
 #endif
 /* ---------------------------------------------------------------- batch: stencils */
@@ -811,14 +790,12 @@ void gsh_blur_sobel_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned
   hipStream_t st = ctx().s();
   if (radius >= 1 && radius <= 3 && strip_ok(w, h) && h >= 3 &&
       h > 2 * radius) {
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-      const unsigned nn = std::min(kMaxZ, n - f0);
+    for_frames(n, [&](unsigned f0, unsigned nn) {
       const int rg = strip_mode(w, src + fb * f0);
       const StripCfg c = strip_cfg(w, h - 2, nn, 3, 2, 8, rg);
-      launch_blur_sobel(radius, dim3(c.grid.x, c.grid.y, nn), c.block, st, dst + fb * f0, src + fb * f0, w, h,
-                        c.T, fb, rg);
+      launch_blur_sobel(radius, dim3(c.grid.x, c.grid.y, nn), c.block, st, dst + fb * f0, src + fb * f0, w, h, c.T, fb, rg);
       GS_LAUNCH(k_zero_frame, dim3((2 * w + 2 * h + 255) / 256, nn), dim3(256), 0, st, dst + fb * f0, w, h, fb);
-    }
+    });
     return;
   }
   uint8_t *t = (uint8_t *)ctx().scratch(SL_AUX, fb * n);
@@ -831,10 +808,11 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
   GS_ASSERT(dst && src && hist_scratch && thr && w > 0 && h > 0);
   const size_t fb = (size_t)w * h;
   hipStream_t st = ctx().s();
-  auto zero_frame = [&]() { /* gs_sobel ran "into a zeroed image": only its 1-px frame is left */
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ)
-      GS_LAUNCH(k_zero_frame, dim3((2 * w + 2 * h + 255) / 256, std::min(kMaxZ, n - f0)), dim3(256), 0,
-                st, dst + fb * f0, w, h, fb);
+  /* gs_sobel ran "into a zeroed image": only its 1-px frame is left; frames [f0, f0 + nn) on stream `on` */
+  auto zero_frame = [&](hipStream_t on, unsigned f0, unsigned nn) {
+    for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
+      GS_LAUNCH(k_zero_frame, dim3((2 * w + 2 * h + 255) / 256, m), dim3(256), 0, on, dst + fb * g0, w, h, fb);
+    });
   };
   if (!tmp && radius >= 1 && radius <= 3 && strip_ok16(w, h, dst, src) && w >= 32 &&
       h >= 3 && h > 2 * radius) { /* every window is clipped on at most one side per axis */
@@ -844,7 +822,7 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
      * back to back on the caller's stream, each chunk's histogram reduce / Otsu / frame zeroing /
      * threshold pass on a side stream behind one event, i.e. under the next chunk's fused kernel.
      * gsh_tune key 5: frames per chunk (0 = default, negative = never split). */
-    const int tune_chunk = g_tune[5];
+    const int tune_chunk = g_tune[GSH_TUNE_PIPELINE_CHUNK];
     const unsigned per = tune_chunk < 0 ? n : tune_chunk > 0 ? (unsigned)tune_chunk : kChunkFrames;
     /* chunk sizes: `per` frames each.  (Tapering the tail -- 16, 8, 8 -- so that less of the last
      * threshold pass is exposed measured slower: small fused launches cost more than they hide.) */
@@ -860,8 +838,7 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
     unsigned *partial = (unsigned *)ctx().scratch(SL_HISTP, (size_t)n * bpf_max * 256 * 4);
     auto run_fused = [&](hipStream_t on, unsigned f0, unsigned nn) {
       const StripCfg c = cfg_for(nn);
-      for (unsigned g0 = f0; g0 < f0 + nn; g0 += kMaxZ) {
-        const unsigned m = std::min(kMaxZ, f0 + nn - g0);
+      for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
         const dim3 grid(c.grid.x, c.grid.y, m);
         uint8_t *d = dst + fb * g0;
         const uint8_t *sp = src + fb * g0;
@@ -873,27 +850,23 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
 #ifndef GS_EMU
         ctx().prof_mark(1, on);
 #endif
-      }
+      });
     };
     auto run_rest = [&](hipStream_t on, unsigned f0, unsigned nn) {
       const StripCfg c = cfg_for(nn);
       const unsigned bpf = c.grid.x * c.grid.y;
-      for (unsigned g0 = f0; g0 < f0 + nn; g0 += kMaxZ) {
-        const unsigned m = std::min(kMaxZ, f0 + nn - g0);
+      for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
         const unsigned *pp = partial + (size_t)g0 * bpf_max * 256;
         /* the 2w + 2(h-2) frame pixels are 0 in the result and were not counted by the kernel; the threshold pass
          * below waits for this launch only (k_otsu folds the blocks' partial histograms itself) */
         GS_LAUNCH(k_otsu, dim3(m), dim3(256), 0, on, hist_scratch + (size_t)g0 * 256, w * h, thr + g0, pp, bpf,
                   2 * w + 2 * (h - 2));
-      }
+      });
       launch_threshold(dst + fb * f0, fb, nn, thr + f0, 0, on);
       /* gs_sobel ran "into a zeroed image": only its 1-px frame is left to zero.  AFTER the threshold pass (which
        * turns whatever the fused kernel left there into 0 / 255): the frame is then 0 either way, and the
        * threshold pass need not wait for this launch. */
-      for (unsigned g0 = f0; g0 < f0 + nn; g0 += kMaxZ) {
-        const unsigned m = std::min(kMaxZ, f0 + nn - g0);
-        GS_LAUNCH(k_zero_frame, dim3((2 * w + 2 * h + 255) / 256, m), dim3(256), 0, on, dst + fb * g0, w, h, fb);
-      }
+      zero_frame(on, f0, nn);
     };
 #ifdef GS_EMU
     const bool split = false;
@@ -942,7 +915,7 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
    * which then need not preserve columns 0 / w-1 */
   if (w < 3 || h < 3) GS_HIP(hipMemsetAsync(dst, 0, fb * n, st));
   launch_sobel(dst, t, w, h, n, false);
-  if (w >= 3 && h >= 3) zero_frame();
+  if (w >= 3 && h >= 3) zero_frame(st, 0, n);
   launch_otsu(dst, w, h, n, hist_scratch, thr);
   launch_threshold(dst, fb, n, thr, 0);
 }
@@ -977,42 +950,31 @@ void gsh_filter_batch(uint8_t *dst, const uint8_t *src, unsigned w, unsigned h, 
     fk.mul = (0x1000000u + norm - 1u) / norm;
     fk.cap = std::min(255u * norm, 32767u) * 0x10001u;
     fk.neg_is_255 = norm > 1 ? 0xffffffffu : 0u;
-    for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-      const unsigned nn = std::min(kMaxZ, n - f0);
+    for_frames(n, [&](unsigned f0, unsigned nn) {
       const int rg = strip_mode(w, src + fb * f0);
       const StripCfg c = strip_cfg(w, h, nn, 6, 2, 8, rg);
       uint8_t *d = dst + fb * f0;
       const uint8_t *s = src + fb * f0;
       const size_t fa = fb | c.xcd_flag;
-      if (norm == 1) { /* multiplier 2^24: a shift (k_stencil.h) */
-        if (rg == 1) GS_LAUNCH((k_filter16<1, true>), c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk);
-        else if (rg == 2) GS_LAUNCH((k_filter16<2, true>), c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk);
-        else GS_LAUNCH((k_filter16<0, true>), c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk);
-      } else if (rg == 1) GS_LAUNCH(k_filter16<1>, c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk);
-      else if (rg == 2) GS_LAUNCH(k_filter16<2>, c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk);
-      else GS_LAUNCH(k_filter16<0>, c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk);
-    }
+      with_const<false, true>(norm == 1, [&](auto SHIFT) { /* multiplier 2^24: a shift (k_stencil.h) */
+        with_const<0, 1, 2>(rg, [&](auto RG) { GS_LAUNCH((k_filter16<GS_CV(RG), GS_CV(SHIFT)>), c.grid, c.block, 0, st, d, s, w, h, c.T, fa, fk); });
+      });
+    });
     return;
   }
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    GS_LAUNCH(k_filter_px, grid2d(w, h, nn), dim3(64, 4), 0, st, dst + fb * f0, src + fb * f0, w, h,
-              fb, (const int8_t *)dk, kw, kh, norm);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_filter_px, grid2d(w, h, nn), dim3(64, 4), 0, st, dst + fb * f0, src + fb * f0, w, h, fb, (const int8_t *)dk, kw, kh, norm);
+  });
 }
 void gsh_downsample_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n) {
   GS_ASSERT(dst && src && sw > 1 && sh > 1);
   hipStream_t st = ctx().s();
   const size_t sfb = (size_t)sw * sh, dfb = (size_t)(sw / 2) * (sh / 2);
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     if (sw >= 16)
-      GS_LAUNCH(k_downsample8, dim3(((sw / 2 + 7) / 8 + 63) / 64, (sh / 2 + 3) / 4, nn), dim3(64, 4), 0, st,
-                dst + dfb * f0, src + sfb * f0, sw, sh);
-    else
-      GS_LAUNCH(k_downsample_px, grid2d(sw / 2, sh / 2, nn), dim3(64, 4), 0, st, dst + dfb * f0,
-                src + sfb * f0, sw, sh);
-  }
+      GS_LAUNCH(k_downsample8, dim3(((sw / 2 + 7) / 8 + 63) / 64, (sh / 2 + 3) / 4, nn), dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh);
+    else GS_LAUNCH(k_downsample_px, grid2d(sw / 2, sh / 2, nn), dim3(64, 4), 0, st, dst + dfb * f0, src + sfb * f0, sw, sh);
+  });
 }
 
 /* levels 1 .. L-1 of n frames in one launch per kMaxZ frames (k_pyramid); the level rule is the ORB driver's
@@ -1030,11 +992,10 @@ void gsh_pyramid_batch(uint8_t *levels_dev, const uint8_t *img_dev, unsigned w, 
     fb[l] = l < L ? (size_t)lw[l] * lh[l] : 0;
     if (l + 1 < 4) plane[l + 1] = plane[l] + fb[l] * n;
   }
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     GS_LAUNCH(k_pyramid, dim3(((w + 15) / 16 + 63) / 64, ((h + 7) / 8 + 3) / 4, nn), dim3(64, 4), 0, st, plane[1] + fb[1] * f0,
               plane[2] + fb[2] * f0, plane[3] + fb[3] * f0, img_dev + fb[0] * f0, w, h, L);
-  }
+  });
 }
 
 void gsh_crop_batch(uint8_t *dst, const uint8_t *src, unsigned sw, unsigned sh, unsigned n, struct gs_rect roi) {
@@ -1105,15 +1066,13 @@ void gsh_synth_batch(uint8_t *dst, unsigned w, unsigned h, unsigned n, uint32_t 
   }
   const unsigned nlev = ((w + 31) / 32) * ((h + 31) / 32);
   const size_t npx = (size_t)w * h;
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
     uint8_t *lev = (uint8_t *)ctx().scratch(SL_LEV, (size_t)nlev * nn);
     const unsigned per = 256 * kSynthRun;
-    GS_LAUNCH(k_synth_levels, dim3((nlev + per - 1) / per, nn), dim3(256), 0, st, lev, nlev,
+    GS_LAUNCH(k_synth_levels, dim3((nlev + per - 1) / per, nn), dim3(256), 0, st, lev, nlev, seed0 + f0, (const SynthJump *)dj);
+    GS_LAUNCH(k_synth_pixels, dim3((unsigned)((npx + per - 1) / per), nn), dim3(256), 0, st, dst + npx * f0, (const uint8_t *)lev, w, h,
               seed0 + f0, (const SynthJump *)dj);
-    GS_LAUNCH(k_synth_pixels, dim3((unsigned)((npx + per - 1) / per), nn), dim3(256), 0, st,
-              dst + npx * f0, (const uint8_t *)lev, w, h, seed0 + f0, (const SynthJump *)dj);
-  }
+  });
 }
 void gsh_checksum_batch(const uint8_t *img, size_t frame_bytes, unsigned n, uint64_t *sums) {
   GS_ASSERT(img && sums && frame_bytes > 0);
@@ -1121,51 +1080,30 @@ void gsh_checksum_batch(const uint8_t *img, size_t frame_bytes, unsigned n, uint
   hipStream_t st = ctx().s();
   GS_HIP(hipMemsetAsync(sums, 0, (size_t)n * 8, st));
   const unsigned bx = (unsigned)std::max<size_t>(1, std::min<size_t>((frame_bytes + 4095) / 4096, 256));
-  for (unsigned f0 = 0; f0 < n; f0 += kMaxZ) {
-    const unsigned nn = std::min(kMaxZ, n - f0);
-    GS_LAUNCH(k_checksum, dim3(bx, nn), dim3(256), 0, st, img + frame_bytes * f0, frame_bytes,
-              (unsigned long long *)sums + f0);
-  }
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_checksum, dim3(bx, nn), dim3(256), 0, st, img + frame_bytes * f0, frame_bytes, (unsigned long long *)sums + f0);
+  });
 }
 
 /* =====================================================================================
  *              drop-in functions: the reference's own names and signatures
  * ===================================================================================== */
 
-/* dst written in full by the kernel: upload src, run, download dst */
-static void unary_full(struct gs_image dst, struct gs_image src,
-                       void (*run)(uint8_t *, const uint8_t *, unsigned, unsigned, unsigned,
-                                   unsigned, int),
-                       unsigned p0, int p1) {
-  const size_t nb = (size_t)src.w * src.h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, nb) : dst.data;
-  run(d, s, src.w, src.h, 1, p0, p1);
-  if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, nb, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
-}
-
 void gs_blur(struct gs_image dst, struct gs_image src, unsigned radius) { /* ref :268 */
   GS_ASSERT(GS_VALID(src) && GS_VALID(dst) && dst.w == src.w && dst.h == src.h);
-  unary_full(dst, src, [](uint8_t *d, const uint8_t *s, unsigned w, unsigned h, unsigned n,
-                          unsigned r, int) { launch_blur(d, s, w, h, n, r); }, radius, 0);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { launch_blur(d, s, src.w, src.h, 1, radius); });
 }
 void gs_erode(struct gs_image dst, struct gs_image src) { /* ref :303 */
   GS_ASSERT(GS_VALID(dst) && GS_VALID(src) && dst.w == src.w && dst.h == src.h);
-  unary_full(dst, src, [](uint8_t *d, const uint8_t *s, unsigned w, unsigned h, unsigned n,
-                          unsigned, int) { launch_morph<false>(d, s, w, h, n); }, 0, 0);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { launch_morph<false>(d, s, src.w, src.h, 1); });
 }
 void gs_dilate(struct gs_image dst, struct gs_image src) { /* ref :304 */
   GS_ASSERT(GS_VALID(dst) && GS_VALID(src) && dst.w == src.w && dst.h == src.h);
-  unary_full(dst, src, [](uint8_t *d, const uint8_t *s, unsigned w, unsigned h, unsigned n,
-                          unsigned, int) { launch_morph<true>(d, s, w, h, n); }, 0, 0);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { launch_morph<true>(d, s, src.w, src.h, 1); });
 }
 void gs_adaptive_threshold(struct gs_image dst, struct gs_image src, unsigned radius, int c) {
   GS_ASSERT(GS_VALID(dst) && GS_VALID(src) && dst.w == src.w && dst.h == src.h); /* ref :232 */
-  unary_full(dst, src, [](uint8_t *d, const uint8_t *s, unsigned w, unsigned h, unsigned n,
-                          unsigned r, int cc) { launch_box_generic<1>(d, s, w, h, n, r, cc); },
-             radius, c);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { launch_box_generic<1>(d, s, src.w, src.h, 1, radius, c); });
 }
 
 void gs_sobel(struct gs_image dst, struct gs_image src) { /* ref :306 */
@@ -1173,10 +1111,10 @@ void gs_sobel(struct gs_image dst, struct gs_image src) { /* ref :306 */
   const unsigned w = src.w, h = src.h;
   if (w < 3 || h < 3) return; /* reference loops are empty */
   const size_t nb = (size_t)w * h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, nb) : dst.data;
-  if (dhost) {
+  const uint8_t *s = stage_in(src.data, nb, SL_IN);
+  const Staged<uint8_t> out(dst.data, nb, SL_OUT);
+  uint8_t *d = out.dev;
+  if (out.host) {
     /* The 1-px frame of dst is never written (ref :308-309).  Rows 0 / h-1 are simply not copied
      * back; columns 0 / w-1 of the other rows are planted into the device copy (2h bytes up) so
      * rows 1..h-2 can come back as ONE contiguous copy (a pitched interior copy is 3x slower). */
@@ -1188,14 +1126,13 @@ void gs_sobel(struct gs_image dst, struct gs_image src) { /* ref :306 */
     ctx().sync(); /* cols is a local */
   }
   launch_sobel(d, s, w, h, 1, true);
-  if (dhost)
-    GS_HIP(hipMemcpyAsync(dst.data + w, d + w, (size_t)w * (h - 2), hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
+  if (out.host) GS_HIP(hipMemcpyAsync(dst.data + w, d + w, (size_t)w * (h - 2), hipMemcpyDeviceToHost, ctx().s())); /* the interior rows only */
+  finish(out.host);
 }
 
 void gs_filter(struct gs_image dst, struct gs_image src, struct gs_image kernel, unsigned norm) {
   GS_ASSERT(GS_VALID(src) && GS_VALID(dst) && dst.w == src.w && dst.h == src.h && norm > 0);
-  const size_t nb = (size_t)src.w * src.h, kb = (size_t)kernel.w * kernel.h;
+  const size_t kb = (size_t)kernel.w * kernel.h;
   /* ref :260-261: the kernel is read through gs_get, so an invalid kernel contributes nothing */
   std::vector<int8_t> k(std::max<size_t>(1, kb), 0);
   unsigned kw = kernel.w, kh = kernel.h;
@@ -1206,79 +1143,50 @@ void gs_filter(struct gs_image dst, struct gs_image src, struct gs_image kernel,
     kw = kh = 1; /* empty loop in the reference: sum = 0 */
     k[0] = 0;
   }
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, nb) : dst.data;
-  gsh_filter_batch(d, s, src.w, src.h, 1, k.data(), kw, kh, norm);
-  if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, nb, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { gsh_filter_batch(d, s, src.w, src.h, 1, k.data(), kw, kh, norm); });
 }
 
 void gs_downsample(struct gs_image dst, struct gs_image src) { /* ref :189 */
   GS_ASSERT(GS_VALID(src) && GS_VALID(dst) && dst.w == src.w / 2 && dst.h == src.h / 2);
-  const size_t nb = (size_t)src.w * src.h, db = (size_t)dst.w * dst.h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, db) : dst.data;
-  gsh_downsample_batch(d, s, src.w, src.h, 1);
-  if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, db, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { gsh_downsample_batch(d, s, src.w, src.h, 1); });
 }
 
 /* ---- geometry + template matching ------------------------------------------ */
 void gs_crop(struct gs_image dst, struct gs_image src, struct gs_rect roi) { /* ref :154 */
   GS_ASSERT(GS_VALID(dst) && GS_VALID(src) && roi.x + roi.w <= src.w && roi.y + roi.h <= src.h &&
             dst.w == roi.w && dst.h == roi.h);
-  const size_t nb = (size_t)src.w * src.h, db = (size_t)dst.w * dst.h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, db) : dst.data;
-  if (roi.x <= src.w && roi.w <= src.w - roi.x && roi.y <= src.h && roi.h <= src.h - roi.y)
-    launch_crop(d, s, src.w, src.h, 1, roi);
-  else /* accepted only because the reference's sums wrap: its gs_get semantics pixel by pixel */
-    GS_LAUNCH(k_crop_wrapped, dim3((roi.w + 63) / 64, (roi.h + 3) / 4), dim3(64, 4), 0, ctx().s(), d, s, src.w, src.h, roi.x,
-              roi.y, roi.w, roi.h);
-  if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, db, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) {
+    if (roi.x <= src.w && roi.w <= src.w - roi.x && roi.y <= src.h && roi.h <= src.h - roi.y)
+      launch_crop(d, s, src.w, src.h, 1, roi);
+    else /* accepted only because the reference's sums wrap: its gs_get semantics pixel by pixel */
+      GS_LAUNCH(k_crop_wrapped, dim3((roi.w + 63) / 64, (roi.h + 3) / 4), dim3(64, 4), 0, ctx().s(), d, s, src.w, src.h, roi.x, roi.y,
+                roi.w, roi.h);
+  });
 }
 void gs_copy(struct gs_image dst, struct gs_image src) { /* ref :160 */
   const struct gs_rect all = {0, 0, src.w, src.h};
   gs_crop(dst, src, all);
 }
 static void resize_common(struct gs_image dst, struct gs_image src, bool nearest) {
-  const size_t nb = (size_t)src.w * src.h, db = (size_t)dst.w * dst.h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, nb, SL_IN);
-  const bool dhost = !is_dev(dst.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, db) : dst.data;
-  launch_resize(d, dst.w, dst.h, s, src.w, src.h, 1, nullptr, nullptr, 1, nearest);
-  if (dhost) GS_HIP(hipMemcpyAsync(dst.data, d, db, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
-}
-void gs_resize_nn(struct gs_image dst, struct gs_image src) { /* ref :164 (asserts nothing there) */
   GS_ASSERT(GS_VALID(dst) && GS_VALID(src));
-  resize_common(dst, src, true);
+  image_to_image(dst, src, [&](uint8_t *d, const uint8_t *s) { launch_resize(d, dst.w, dst.h, s, src.w, src.h, 1, nullptr, nullptr, 1, nearest); });
 }
-void gs_resize(struct gs_image dst, struct gs_image src) { /* ref :171 */
-  GS_ASSERT(GS_VALID(dst) && GS_VALID(src));
-  resize_common(dst, src, false);
-}
+void gs_resize_nn(struct gs_image dst, struct gs_image src) { resize_common(dst, src, true); } /* ref :164 (asserts nothing there) */
+void gs_resize(struct gs_image dst, struct gs_image src) { resize_common(dst, src, false); }   /* ref :171 */
 void gs_match_template(struct gs_image img, struct gs_image tmpl, struct gs_image result) { /* ref :705 */
   GS_ASSERT(GS_VALID(img) && GS_VALID(tmpl) && GS_VALID(result));
   GS_ASSERT(img.w >= tmpl.w && img.h >= tmpl.h);
   GS_ASSERT(result.w == img.w - tmpl.w + 1 && result.h == img.h - tmpl.h + 1);
   const size_t ib = (size_t)img.w * img.h, tb = (size_t)tmpl.w * tmpl.h, rb = (size_t)result.w * result.h;
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, ib, SL_IN);
-  const uint8_t *t = (const uint8_t *)stage_in(tmpl.data, tb, SL_AUX);
-  const bool dhost = !is_dev(result.data);
-  uint8_t *d = dhost ? (uint8_t *)ctx().scratch(SL_OUT, rb) : result.data;
-  tm_launch(s, img.w, img.h, 1, t, tmpl.w, tmpl.h, 1, d, nullptr); /* the batch launcher with one frame: route and tile form as ever */
-  if (dhost) GS_HIP(hipMemcpyAsync(result.data, d, rb, hipMemcpyDeviceToHost, ctx().s()));
-  finish(dhost);
+  const uint8_t *s = stage_in(img.data, ib, SL_IN), *t = stage_in(tmpl.data, tb, SL_AUX);
+  const Staged<uint8_t> d(result.data, rb, SL_OUT);
+  tm_launch(s, img.w, img.h, 1, t, tmpl.w, tmpl.h, 1, d.dev, nullptr); /* the batch launcher with one frame: route and tile form as ever */
+  d.done();
 }
 struct gs_point gs_find_best_match(struct gs_image result) { /* ref :726 */
   GS_ASSERT(GS_VALID(result));
   const unsigned long long n = (unsigned long long)result.w * result.h;
-  const uint8_t *s = (const uint8_t *)stage_in(result.data, (size_t)n, SL_IN);
+  const uint8_t *s = stage_in(result.data, (size_t)n, SL_IN);
   const unsigned blocks = (unsigned)((n + 2047) / 2048);
   unsigned long long *part = (unsigned long long *)ctx().scratch(SL_PFX, (size_t)blocks * 8);
   GS_LAUNCH(k_argmax_first, dim3(blocks), dim3(256), 0, ctx().s(), s, n, part, (unsigned long long *)nullptr);
@@ -1298,18 +1206,16 @@ struct gs_point gs_find_best_match(struct gs_image result) { /* ref :726 */
 void gs_histogram(struct gs_image img, unsigned hist[256]) { /* ref :199 */
   GS_ASSERT(GS_VALID(img) && hist != NULL);
   const size_t nb = (size_t)(img.w * img.h);
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, nb, SL_IN);
-  const bool hhost = !is_dev(hist);
-  unsigned *dh = hhost ? (unsigned *)ctx().scratch(SL_HIST, 1024) : hist;
-  launch_histogram(s, nb, 1, dh);
-  if (hhost) GS_HIP(hipMemcpyAsync(hist, dh, 1024, hipMemcpyDeviceToHost, ctx().s()));
-  finish(hhost);
+  const uint8_t *s = stage_in(img.data, nb, SL_IN);
+  const Staged<unsigned> dh(hist, 1024, SL_HIST);
+  launch_histogram(s, nb, 1, dh.dev);
+  dh.done();
 }
 
 uint8_t gs_otsu_threshold(struct gs_image img) { /* ref :205 */
   GS_ASSERT(GS_VALID(img));
   const size_t nb = (size_t)(img.w * img.h);
-  const uint8_t *s = (const uint8_t *)stage_in(img.data, nb, SL_IN);
+  const uint8_t *s = stage_in(img.data, nb, SL_IN);
   unsigned *dh = (unsigned *)ctx().scratch(SL_HIST, 1024);
   uint8_t *dt = (uint8_t *)ctx().scratch(SL_THR, 16);
   launch_otsu(s, img.w, img.h, 1, dh, dt);
@@ -1322,23 +1228,18 @@ uint8_t gs_otsu_threshold(struct gs_image img) { /* ref :205 */
 void gs_threshold(struct gs_image img, uint8_t thresh) { /* ref :225 */
   GS_ASSERT(GS_VALID(img));
   const size_t nb = (size_t)(img.w * img.h);
-  const bool host = !is_dev(img.data);
-  uint8_t *d = host ? (uint8_t *)ctx().scratch(SL_IN, nb) : img.data;
-  if (host) GS_HIP(hipMemcpyAsync(d, img.data, nb, hipMemcpyHostToDevice, ctx().s()));
-  launch_threshold(d, nb, 1, nullptr, thresh);
-  if (host) GS_HIP(hipMemcpyAsync(img.data, d, nb, hipMemcpyDeviceToHost, ctx().s()));
-  finish(host);
+  const Staged<uint8_t> d(img.data, nb, SL_IN, /*copy_in=*/true);
+  launch_threshold(d.dev, nb, 1, nullptr, thresh);
+  d.done();
 }
 
 void gs_integral(struct gs_image src, unsigned *ii) { /* ref :744 */
   GS_ASSERT(GS_VALID(src) && ii);
   const size_t np = (size_t)src.w * src.h;
-  const uint8_t *s = (const uint8_t *)stage_in(src.data, np, SL_IN);
-  const bool host = !is_dev(ii);
-  unsigned *d = host ? (unsigned *)ctx().scratch(SL_II, np * 4) : ii;
-  launch_integral(s, src.w, src.h, 1, d);
-  if (host) GS_HIP(hipMemcpyAsync(ii, d, np * 4, hipMemcpyDeviceToHost, ctx().s()));
-  finish(host);
+  const uint8_t *s = stage_in(src.data, np, SL_IN);
+  const Staged<unsigned> d(ii, np * 4, SL_II);
+  launch_integral(s, src.w, src.h, 1, d.dev);
+  d.done();
 }
 
 }  /* extern "C" */
