@@ -163,6 +163,10 @@ _SIGS = {
     "gsh_find_best_match_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
     "gsh_locate_template_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
                                           C.c_void_p, C.c_void_p]),
+    "gsh_match_templates_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                         C.c_void_p]),
+    "gsh_locate_templates_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsh_blobs_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_uint]),
     "gsh_blob_corners_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
@@ -659,6 +663,20 @@ class Grayskull:
         n, ih, iw = self._nhw(img)
         tw, th, ntmpl = self._templates(tmpl, n)
         self.c.gsh_locate_template_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, ntmpl, _ptr(best), _ptr(score))
+
+    def match_templates_batch(self, result, img, tmpl):
+        """gsh_match_templates_batch: result (n, m, ih - th + 1, iw - tw + 1) = gs_match_template of every frame of img
+        (n, ih, iw) uint8 against every template of the bank tmpl (m, th, tw)"""
+        n, ih, iw = img.shape
+        m, th, tw = tmpl.shape
+        self.c.gsh_match_templates_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, m, _ptr(result))
+
+    def locate_templates_batch(self, img, tmpl, best, score=None, winner=None):
+        """gsh_locate_templates_batch: best (n, m, 2) int32 {x, y} and score (n, m) uint8 of match_templates_batch's maps without
+        the maps; winner (n) int32: per frame the template with the highest score, the lowest index on ties"""
+        n, ih, iw = img.shape
+        m, th, tw = tmpl.shape
+        self.c.gsh_locate_templates_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, m, _ptr(best), _ptr(score), _ptr(winner))
 
     def blobs_batch(self, img, labels, blobs, counts, nblobs):
         """gsh_blobs_batch: img (n, h, w) uint8, labels (n, h, w) uint16 [or int16], blobs (n, nblobs, 8) int32 (one

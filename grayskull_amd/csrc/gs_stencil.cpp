@@ -602,38 +602,50 @@ template <class F> static void tm_variant(unsigned form, unsigned nkc, F &&f) {
     });
   });
 }
+/* the window sums of (I - 128)^2 of nn frames, rw x rh u32 per frame (SL_PAD; the prefix table they come from: SL_II).  They
+ * depend on the template's SIZE only; have: a launch of the same frames and size left them there, nothing is launched. */
+static unsigned *tm_window_sums(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, unsigned tw, unsigned th, bool have) {
+  const unsigned rw = iw - tw + 1, rh = ih - th + 1;
+  const size_t ib = (size_t)iw * ih, rb = (size_t)rw * rh;
+  hipStream_t st = ctx().s();
+  unsigned *rowp = (unsigned *)ctx().scratch(SL_II, (size_t)nn * ih * (iw + 1) * 4);
+  unsigned *s2 = (unsigned *)ctx().scratch(SL_PAD, (size_t)nn * rb * 4);
+  if (have) return s2;
+  /* four corners of the banded integral table of squares (round 4) for frames of 4 Mpx and
+   * more -- 4K, 128 x 128: 0.269 -> 0.249 ms, 64 x 64: 0.135 -> 0.125; on a 720p frame the four short launches are 6-10 us
+   * SLOWER than the two passes of round 3 (row prefix + sliding columns), which stay for small frames, for key 20 = 4 and
+   * for geometries the banded integral does not take (key 20 = 5: the table route whatever the size);
+   * profiles/r04v_match_template_integral_squares.log */
+  if (g_tune[GSH_TUNE_TMATCH] != 4 && (ib >= (4u << 20) || g_tune[GSH_TUNE_TMATCH] == 5) && launch_integral(s, iw, ih, nn, rowp, /*sq=*/true)) {
+    GS_LAUNCH(k_tm_s2_corners, dim3((rw + 255) / 256, rh, nn), dim3(256), 0, st, (const unsigned *)rowp, iw, ih, tw, th, rw, rh, s2);
+  } else {
+    GS_LAUNCH(k_tm_rowprefix, dim3((ih + 3) / 4, 1, nn), dim3(64, 4), 0, st, s, iw, ih, rowp);
+    GS_LAUNCH(k_tm_colsq, dim3((rw + 63) / 64, (rh + kTmRun - 1) / kTmRun, nn), dim3(64), 0, st, (const unsigned *)rowp, iw, ih, tw, th,
+              rw, rh, s2);
+  }
+  return s2;
+}
 /* nn frames (iw x ih, back to back) against one template (ntmpl == 1) or template f for frame f (ntmpl == nn) in one set of
- * launches on the current stream.  d: the nn result maps; d == nullptr (matrix-core route only): the locate epilogue, keys[f]
- * (zeroed, stream-ordered, before this call) receives frame f's best key. */
+ * launches on the current stream.  d: the nn result maps, rstep bytes apart (0: rw * rh, back to back); d == nullptr (matrix-core
+ * route only): the locate epilogue, keys[f] (zeroed, stream-ordered, before this call) receives frame f's best key.
+ * have_s2: the call before this one was for these frames and this template size (a loop over a bank, tm_bank). */
 static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, const uint8_t *t, unsigned tw, unsigned th, unsigned ntmpl,
-                      uint8_t *d, unsigned long long *keys) {
+                      uint8_t *d, unsigned long long *keys, size_t rstep = 0, bool have_s2 = false) {
   const unsigned rw = iw - tw + 1, rh = ih - th + 1;
   const size_t ib = (size_t)iw * ih, tb = (size_t)tw * th, rb = (size_t)rw * rh;
   const TmRoute route = tm_route(iw, ih, tw, th);
   hipStream_t st = ctx().s();
+  if (!rstep) rstep = rb;
   if (route == TM_MFMA) {
     TmForm f = tm_form(tw, th, rw, rh, nn);
     if (f.lds > 150 * 1024) f = tm_form(tw, th, rw, rh, 1); /* the form one frame takes fits (tm_route) */
     const bool tm_split = f.split, tm_band = f.band;
     const unsigned nkc = (tw + 31 + 31) / 32, istride = f.istride, tstride = 32 * nkc + 48;
     const size_t tm_lds = f.lds, tpb = (size_t)th * tstride; /* tstride is a multiple of 16 */
-    unsigned *rowp = (unsigned *)ctx().scratch(SL_II, (size_t)nn * ih * (iw + 1) * 4);
-    unsigned *s2 = (unsigned *)ctx().scratch(SL_PAD, (size_t)nn * rb * 4);
     uint8_t *tpad = (uint8_t *)ctx().scratch(SL_PRE, ntmpl * tpb + (size_t)ntmpl * 4 + 16);
     unsigned *tsqp = (unsigned *)(tpad + ((ntmpl * tpb + 3) & ~(size_t)3));
     GS_LAUNCH(k_tm_prep, dim3(ntmpl), dim3(1024), 0, st, t, tw, th, tstride, tpad, tsqp);
-    /* window sums of (I - 128)^2: four corners of the banded integral table of squares (round 4) for frames of 4 Mpx and
-     * more -- 4K, 128 x 128: 0.269 -> 0.249 ms, 64 x 64: 0.135 -> 0.125; on a 720p frame the four short launches are 6-10 us
-     * SLOWER than the two passes of round 3 (row prefix + sliding columns), which stay for small frames, for key 20 = 4 and
-     * for geometries the banded integral does not take (key 20 = 5: the table route whatever the size);
-     * profiles/r04v_match_template_integral_squares.log */
-    if (g_tune[GSH_TUNE_TMATCH] != 4 && (ib >= (4u << 20) || g_tune[GSH_TUNE_TMATCH] == 5) && launch_integral(s, iw, ih, nn, rowp, /*sq=*/true)) {
-      GS_LAUNCH(k_tm_s2_corners, dim3((rw + 255) / 256, rh, nn), dim3(256), 0, st, (const unsigned *)rowp, iw, ih, tw, th, rw, rh, s2);
-    } else {
-      GS_LAUNCH(k_tm_rowprefix, dim3((ih + 3) / 4, 1, nn), dim3(64, 4), 0, st, s, iw, ih, rowp);
-      GS_LAUNCH(k_tm_colsq, dim3((rw + 63) / 64, (rh + kTmRun - 1) / kTmRun, nn), dim3(64), 0, st, (const unsigned *)rowp, iw, ih, tw, th,
-                rw, rh, s2);
-    }
+    const unsigned *s2 = tm_window_sums(s, iw, ih, nn, tw, th, have_s2);
 #ifndef GS_EMU
     /* more than the default 64 KB of dynamic LDS: a per-DEVICE attribute of the function (a thread that moved to
      * another device with gsh_set_device kept a thread-local "done" flag and the launch failed there) */
@@ -647,7 +659,7 @@ static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, c
     }
 #endif
     TmArgs ta{s, iw, ih, (const uint8_t *)tpad, (const unsigned *)tsqp, tw, th, s2, d, rw, rh, nkc, istride, tstride,
-              ntmpl > 1 ? (unsigned)tpb : 0u, ntmpl > 1 ? 1u : 0u, keys};
+              ntmpl > 1 ? (unsigned)tpb : 0u, ntmpl > 1 ? 1u : 0u, keys, rstep};
     const dim3 grid = tm_split ? dim3((rw + 63) / 64, (rh + 31) / 32, nn) : dim3((rw + 127) / 128, (rh + 63) / 64, nn);
     tm_variant(tm_split ? 1u : tm_band ? 2u : 0u, nkc, [&](TmKernel fn) { GS_LAUNCH(fn, grid, dim3(256), tm_lds, st, ta); });
     return;
@@ -663,11 +675,11 @@ static void tm_launch(const uint8_t *s, unsigned iw, unsigned ih, unsigned nn, c
     /* four results per thread when image rows start 4-byte aligned (see k_match_template4) */
     if (iw % 4 == 0 && ((uintptr_t)s & 3) == 0 && ib < 0x7fffffffull)
       GS_LAUNCH(k_match_template4, dim3((rw + 255) / 256, (rh + 3) / 4, nn), dim3(64, 4), lds, st, s, iw, ih, t, tw, th, tstep,
-                (const unsigned long long *)tsq, d, rw, rh);
+                (const unsigned long long *)tsq, d, rw, rh, rstep);
     else
-      GS_LAUNCH(k_match_template, g, dim3(64, 4), lds, st, s, iw, ih, t, tw, th, tstep, (const unsigned long long *)tsq, d, rw, rh);
+      GS_LAUNCH(k_match_template, g, dim3(64, 4), lds, st, s, iw, ih, t, tw, th, tstep, (const unsigned long long *)tsq, d, rw, rh, rstep);
   } else {
-    GS_LAUNCH(k_match_template_px, g, dim3(64, 4), 0, st, s, iw, ih, t, tw, th, tstep, d, rw, rh);
+    GS_LAUNCH(k_match_template_px, g, dim3(64, 4), 0, st, s, iw, ih, t, tw, th, tstep, d, rw, rh, rstep);
   }
 }
 /* best / score of n maps of rw x rh from their keys; maps == nullptr: the keys are there already */
@@ -707,6 +719,91 @@ static void tm_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, c
     }
   });
   if (!result) GS_LAUNCH(k_best_from_keys, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, rw, (unsigned *)best, score);
+}
+
+/* ---- a bank of m templates of one size against every frame (k_tmatch.h: k_match_bank_mfma) ------------------------------------ */
+struct TmBankForm {
+  bool valid;
+  unsigned nt, ngroups, rb, band, istride, tstride;
+  size_t lds;
+};
+/* The bank kernel takes templates up to 512 wide (32 slots of 16 bytes a row) of at most 32768 taps on frames below 2^31
+ * bytes.  Rows per band: as many as give 32 slots, an even number where it can be (an odd number of slots ends in a zero
+ * slot).  LDS: 38 KB at 16 x 16 and 64 templates, 40 KB at the widest. */
+static TmBankForm tm_bank_form(unsigned iw, unsigned ih, unsigned tw, unsigned th, unsigned m) {
+  TmBankForm f;
+  const unsigned spr = (tw + 15) / 16, rh = ih - th + 1;
+  f.rb = 16 * spr;
+  f.nt = m > 32 ? 2 : 1;
+  f.ngroups = (m + 32 * f.nt - 1) / (32 * f.nt);
+  f.valid = spr <= 32 && (size_t)tw * th <= 32768 && (size_t)iw * ih < 0x7fffffffull && (rh + 7) / 8 <= 65535 && f.ngroups <= 65535;
+  f.band = std::max(1u, 32 / std::max(1u, std::min(spr, 32u)));
+  if (f.band >= 2) f.band &= ~1u;
+  f.band = std::min(f.band, th);
+  const unsigned ns2 = (f.band * spr + 1) & ~1u;
+  f.tstride = (ns2 + 1) * 16, f.istride = 64 + f.rb + 16;
+  f.lds = std::max<size_t>((size_t)(8 + f.band) * f.istride + (size_t)32 * f.nt * f.tstride, 2048 * f.nt);
+  return f;
+}
+/* gsh_tune key 27: 1 the loop over the templates whatever the bank, 2 the bank kernel wherever it is valid; 0: by the
+ * measurement of docs/design/stencils.md 3.5 (profiles/tmatch_bank.json; 32 frames of 720p).  Where one template takes the
+ * dot-product kernels (16 x 16: the loop gains nothing from shared window sums) the bank kernel wins from 4 templates (x 0.63;
+ * 2: x 1.1); where it takes the matrix cores (32 x 32) the loop with the window sums computed once wins up to 8 templates
+ * (0.99 against 1.49 ms) and the bank kernel from 16 (1.71 against 1.82 ms, locate 1.89 against 2.99). */
+constexpr unsigned kTmBankLeastDot = 4, kTmBankLeastMfma = 16;
+/* gsh_match_templates_batch (result != nullptr) and gsh_locate_templates_batch (best != nullptr).  The keys of the locate form
+ * lie template-major, keys[t * n + f], so that a trip of the loop -- one template against a chunk's frames -- fills a run of them */
+static void tm_bank(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th, unsigned m,
+                    uint8_t *result, struct gs_point *best, uint8_t *score, unsigned *winner) {
+  if (n == 0 || m == 0) return;
+  GS_ASSERT(img && iw > 0 && ih > 0 && tmpl && tw > 0 && th > 0 && (result || best));
+  GS_ASSERT(tw <= iw && th <= ih);
+  GS_ASSERT((unsigned long long)n * m <= 0x7fffffffull);
+  const unsigned rw = iw - tw + 1, rh = ih - th + 1;
+  const size_t ib = (size_t)iw * ih, tb = (size_t)tw * th, rb = (size_t)rw * rh;
+  const TmRoute route = tm_route(iw, ih, tw, th);
+  const TmBankForm bf = tm_bank_form(iw, ih, tw, th, m);
+  const int key = g_tune[GSH_TUNE_TMATCH_BANK];
+  const bool bank = bf.valid && key != 1 && (key == 2 || m >= (route == TM_MFMA ? kTmBankLeastMfma : kTmBankLeastDot));
+  unsigned chunk = tm_chunk_frames(bank ? TM_MFMA : route, iw, ih, rw, rh, n, result == nullptr);
+  if (bank) chunk = std::min(chunk, 65535u / bf.ngroups); /* blockIdx.z = frame x template group */
+  hipStream_t st = ctx().s();
+  unsigned long long *keys = nullptr;
+  if (!result) {
+    keys = (unsigned long long *)ctx().scratch(SL_BEST, (size_t)n * m * 8);
+    GS_HIP(hipMemsetAsync(keys, 0, (size_t)n * m * 8, st));
+  }
+  uint8_t *bankp = nullptr;
+  unsigned *tsqp = nullptr;
+  if (bank) {
+    const size_t bb = (size_t)m * th * bf.rb; /* a multiple of 16 */
+    bankp = (uint8_t *)ctx().scratch(SL_PRE, bb + (size_t)m * 4);
+    tsqp = (unsigned *)(bankp + bb);
+    GS_LAUNCH(k_tm_bank_prep, dim3(m), dim3(256), 0, st, tmpl, tw, th, bf.rb, bankp, tsqp);
+  }
+  for_frames(n, chunk, [&](unsigned f0, unsigned nn) {
+    const uint8_t *s = img + ib * f0;
+    if (bank) {
+      const unsigned *s2 = tm_window_sums(s, iw, ih, nn, tw, th, false);
+      TmBankArgs ba{s, iw, ih, (const uint8_t *)bankp, (const unsigned *)tsqp, tw, th, m, s2, result ? result + rb * m * f0 : nullptr, rw, rh,
+                    bf.rb, bf.band, bf.istride, bf.tstride, bf.ngroups, result ? nullptr : keys + f0, n};
+      const dim3 grid((rw + 63) / 64, (rh + 7) / 8, nn * bf.ngroups);
+      with_const<1u, 2u>(bf.nt, [&](auto NT) { GS_LAUNCH(k_match_bank_mfma<GS_CV(NT)>, grid, dim3(256), bf.lds, st, ba); });
+      return;
+    }
+    for (unsigned t = 0; t < m; t++) { /* one template against the chunk's frames; the window sums of trip 0 serve the others */
+      const uint8_t *tp = tmpl + tb * t;
+      if (result) tm_launch(s, iw, ih, nn, tp, tw, th, 1, result + rb * ((size_t)m * f0 + t), nullptr, rb * m, t > 0);
+      else if (route == TM_MFMA) tm_launch(s, iw, ih, nn, tp, tw, th, 1, nullptr, keys + (size_t)t * n + f0, 0, t > 0);
+      else {
+        uint8_t *maps = (uint8_t *)ctx().scratch(SL_OUT, (size_t)nn * rb);
+        tm_launch(s, iw, ih, nn, tp, tw, th, 1, maps, nullptr);
+        tm_argmax(maps, rw, rh, nn, keys + (size_t)t * n + f0);
+      }
+    }
+  });
+  if (!result)
+    GS_LAUNCH(k_tm_bank_best, dim3((n * m + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, m, rw, (unsigned *)best, score, winner);
 }
 
 }  // namespace gsi
@@ -1047,6 +1144,18 @@ void gsh_locate_template_batch(const uint8_t *img, unsigned iw, unsigned ih, uns
   if (n == 0) return;
   GS_ASSERT(best != NULL);
   tm_batch(img, iw, ih, n, tmpl, tw, th, ntmpl, nullptr, best, score);
+}
+void gsh_match_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th,
+                               unsigned m, uint8_t *result) {
+  if (n == 0 || m == 0) return;
+  GS_ASSERT(result != NULL);
+  tm_bank(img, iw, ih, n, tmpl, tw, th, m, result, nullptr, nullptr, nullptr);
+}
+void gsh_locate_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th,
+                                unsigned m, struct gs_point *best, uint8_t *score, unsigned *winner) {
+  if (n == 0 || m == 0) return;
+  GS_ASSERT(best != NULL);
+  tm_bank(img, iw, ih, n, tmpl, tw, th, m, nullptr, best, score, winner);
 }
 
 

@@ -54,15 +54,15 @@ __global__ __launch_bounds__(256) void k_sum_squares(const uint8_t *v, unsigned 
  * of a row go byte by byte.  Row sums (<= tw * 65025 < 2^32 for tw <= 16384) are added to 64-bit
  * totals after every template row.  Requires tw <= kTmplTile - 3 (wider: k_match_template_px). */
 constexpr unsigned kTmplTile = 16384;
-/* The three map kernels take the frame from blockIdx.z: frame f's image lies iw * ih bytes, its result rw * rh bytes behind
- * frame f - 1's; tstep = 0: one template (and one tmpl_sq) for every frame, tstep = tw * th: template f for frame f. */
+/* The three map kernels take the frame from blockIdx.z: frame f's image lies iw * ih bytes, its result rstep bytes (rw * rh, or
+ * more where other maps lie between: a bank of templates) behind frame f - 1's; tstep = 0: one template (and one tmpl_sq) for every frame, tstep = tw * th: template f for frame f. */
 __global__ __launch_bounds__(256) void k_match_template(const uint8_t *img, unsigned iw, unsigned ih,
                                                         const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstep,
                                                         const unsigned long long *tmpl_sq,
-                                                        uint8_t *result, unsigned rw, unsigned rh) {
+                                                        uint8_t *result, unsigned rw, unsigned rh, size_t rstep) {
   GS_DYN_LDS(smem);
   uint8_t *lt = (uint8_t *)smem;
-  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rw * rh;
+  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rstep;
   tmpl += (size_t)blockIdx.z * tstep, tmpl_sq += tstep ? blockIdx.z : 0u;
   const unsigned tid = threadIdx.y * 64u + threadIdx.x;
   const unsigned rx = blockIdx.x * 64u + threadIdx.x, ry = blockIdx.y * 4u + threadIdx.y;
@@ -113,10 +113,10 @@ __global__ __launch_bounds__(256) void k_match_template(const uint8_t *img, unsi
 __global__ __launch_bounds__(256) void k_match_template4(const uint8_t *img, unsigned iw, unsigned ih,
                                                          const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstep,
                                                          const unsigned long long *tmpl_sq,
-                                                         uint8_t *result, unsigned rw, unsigned rh) {
+                                                         uint8_t *result, unsigned rw, unsigned rh, size_t rstep) {
   GS_DYN_LDS(smem);
   uint8_t *lt = (uint8_t *)smem;
-  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rw * rh;
+  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rstep;
   tmpl += (size_t)blockIdx.z * tstep, tmpl_sq += tstep ? blockIdx.z : 0u;
   const unsigned tid = threadIdx.y * 64u + threadIdx.x;
   const unsigned rx0 = (blockIdx.x * 64u + threadIdx.x) * 4u, ry = blockIdx.y * 4u + threadIdx.y;
@@ -178,10 +178,10 @@ __global__ __launch_bounds__(256) void k_match_template4(const uint8_t *img, uns
 /* any template width: one subtract-multiply-add per tap, template read from global memory */
 __global__ __launch_bounds__(256) void k_match_template_px(const uint8_t *img, unsigned iw, unsigned ih,
                                                            const uint8_t *tmpl, unsigned tw, unsigned th, unsigned tstep,
-                                                           uint8_t *result, unsigned rw, unsigned rh) {
+                                                           uint8_t *result, unsigned rw, unsigned rh, size_t rstep) {
   const unsigned rx = blockIdx.x * 64u + threadIdx.x, ry = blockIdx.y * 4u + threadIdx.y;
   if (rx >= rw || ry >= rh) return;
-  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rw * rh, tmpl += (size_t)blockIdx.z * tstep;
+  img += (size_t)blockIdx.z * iw * ih, result += (size_t)blockIdx.z * rstep, tmpl += (size_t)blockIdx.z * tstep;
   unsigned long long sum = 0;
   for (unsigned ty = 0; ty < th; ty++)
     for (unsigned tx = 0; tx < tw; tx++) {

@@ -48,6 +48,7 @@ struct TmArgs {
   /* result == nullptr: the locate epilogue -- no score byte is stored; keys[blockIdx.z] (zeroed before the launch) receives
    * the maximum of score << 32 | ~(ry * rw + rx) over the frame, one 64-bit atomicMax per wave that saw a non-zero score */
   unsigned long long *keys;
+  size_t rstep; /* frame f's result map lies f * rstep bytes behind result: rw * rh, or more where other maps lie between */
 };
 
 /* the template as the MFMA kernel wants it: th rows of tstride bytes (32 zeros, T ^ 0x80, zeros), and sum (T - 128)^2.
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256) void k_match_template_mfma(TmArgs a) {
   { /* this block's frame (scalar arithmetic on the kernel's arguments) */
     const size_t f = blockIdx.z;
     a.img += f * a.iw * a.ih, a.s2 += f * a.rw * a.rh, a.tpad += f * a.tstep, a.tsq += f * a.sqstep;
-    if (a.result) a.result += f * a.rw * a.rh;
+    if (a.result) a.result += f * a.rstep;
   }
   constexpr unsigned TR = SPLIT == 1 ? 64u : 32u, TC = SPLIT == 1 ? 128u : 64u;
   const unsigned bx0 = blockIdx.x * TC, by0 = blockIdx.y * TR;
@@ -390,6 +391,236 @@ __global__ __launch_bounds__(256) void k_match_template_mfma(TmArgs a) {
                     * first maximum whatever order they arrive in; a wave that saw only zeros leaves the key word alone */
     best = wave_max_u64(best);
     if (lane == 0 && (best >> 32)) atomicMax(a.keys + blockIdx.z, best);
+  }
+}
+
+/* ---- A BANK of templates (gsh_match_templates_batch, gsh_locate_templates_batch) -------------------------------------------
+ * m templates of one size against every frame: the cross term is a real matrix product,
+ *   C[t][pos] = sum_k T'_t[k] patch(pos)[k],   M = templates, N = result positions, K = the template's taps,
+ * with no structural zeros in either operand.  The K axis runs over the template row by row, every row padded with zeros to
+ * rb = 16 ceil(tw / 16) bytes, so a K step of 32 is two 16-byte slots and slot s is 16 consecutive taps of row s / (rb / 16):
+ *   A operand of lane (t, g): slot 2 k + g of template t -- one aligned 16-byte LDS read out of the bank;
+ *   B operand of lane (n, g): the 16 image bytes that slot meets at position (x0 + n, y): consecutive lanes are one byte apart,
+ *     so five dword reads and four v_alignbit, as the B operand of k_match_template_mfma; where the template side is padding
+ *     the image side holds whatever lies there.
+ * Positions are the N side so that a register of the result is 32 consecutive bytes of ONE map (templates on the N side would
+ * scatter 4-byte pieces over 32 maps).  A wave owns 4 result rows x 32 columns for NT x 32 templates (4 NT accumulator tiles:
+ * every A operand feeds four MFMAs, every B operand NT), a block 2 x 2 waves = 8 rows x 64 columns; blockIdx.z = frame x
+ * template group of 32 NT.  Templates past m in the last group are zero rows whose results go nowhere.
+ *   The template's rows are taken `band` at a time (a.band rows = at most 32 slots, so the block's share of the bank stays at
+ * 16 NT KB whatever th and m are); a band with an odd number of slots ends with a zero slot.
+ *   Epilogue: the arithmetic of k_match_template_mfma's finish, bit for bit.  Locate form: one key word per (frame, template),
+ * reduced over the lane's rows, the 32 lanes of a template, the block's four waves, and only then sent -- and not sent at all
+ * where the word already holds as much (it only ever grows, so a stale read errs on the side of sending). */
+struct TmBankArgs {
+  const uint8_t *img;
+  unsigned iw, ih;
+  const uint8_t *bank; /* m templates of th rows of rb signed bytes, zero padded (k_tm_bank_prep) */
+  const unsigned *tsq; /* m sums of (T - 128)^2 */
+  unsigned tw, th, m;
+  const unsigned *s2; /* per frame rh x rw window sums of (I - 128)^2 */
+  uint8_t *result;    /* map (f, t) at result + (f m + t) rw rh; nullptr: the locate epilogue */
+  unsigned rw, rh;
+  unsigned rb;      /* bytes of a padded template row */
+  unsigned band;    /* template rows resident at a time */
+  unsigned istride; /* LDS image row: 64 + rb + 16 bytes */
+  unsigned tstride; /* LDS bytes of one template's band: an odd number of 16-byte slots (conflict-free b128 reads) */
+  unsigned ngroups; /* template groups per frame */
+  unsigned long long *keys; /* locate: keys[t * kstride + frame of the launch], zeroed before the launch */
+  unsigned kstride;
+};
+
+/* template b of the bank as the kernel wants it (th rows of rb bytes: T ^ 0x80, zeros) and sum (T - 128)^2.  grid m, block 256 */
+__global__ __launch_bounds__(256) void k_tm_bank_prep(const uint8_t *tmpl, unsigned tw, unsigned th, unsigned rb, uint8_t *bank, unsigned *tsq) {
+  __shared__ unsigned part[4];
+  tmpl += (size_t)blockIdx.x * tw * th, bank += (size_t)blockIdx.x * th * rb, tsq += blockIdx.x;
+  const unsigned tid = threadIdx.x, tdw = rb / 4u, ntd = th * tdw;
+  unsigned t2 = 0;
+  for (unsigned i = tid; i < ntd; i += 256u) {
+    const unsigned j = i / tdw, q = 4u * (i - j * tdw);
+    uint32_t sv = 0;
+    for (unsigned b = 0; b < 4; b++)
+      if (q + b < tw) {
+        const unsigned t = tmpl[(size_t)j * tw + q + b];
+        const int d = (int)t - 128;
+        t2 += (unsigned)(d * d);
+        sv |= (t ^ 0x80u) << (8 * b);
+      }
+    ((uint32_t *)bank)[i] = sv;
+  }
+  t2 = wave_sum(t2);
+  if ((tid & 63u) == 0) part[tid >> 6] = t2;
+  __syncthreads();
+  if (tid == 0) *tsq = part[0] + part[1] + part[2] + part[3];
+}
+
+/* grid (ceil(rw / 64), ceil(rh / 8), frames x a.ngroups), block 256,
+ * dynamic LDS max((8 + band) istride + 32 NT tstride, 2048 NT) */
+template <unsigned NT>
+__global__ __launch_bounds__(256, 2) void k_match_bank_mfma(TmBankArgs a) {
+  GS_DYN_LDS(smem);
+  const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const unsigned fl = blockIdx.z / a.ngroups, tg0 = (blockIdx.z - fl * a.ngroups) * (32u * NT); /* frame of the launch, first template */
+  a.img += (size_t)fl * a.iw * a.ih, a.s2 += (size_t)fl * a.rw * a.rh;
+  const unsigned bx0 = blockIdx.x * 64u, by0 = blockIdx.y * 8u;
+  const unsigned spr = a.rb / 16u; /* slots per template row */
+  uint8_t *limg = (uint8_t *)smem;
+  uint8_t *ltm = limg + (size_t)(8u + a.band) * a.istride; /* a multiple of 16 */
+  const unsigned idw = a.istride / 4u;
+  /* image rows by0 + jc .. + 6 + nj of the block's columns as signed bytes (0 outside the image: such bytes only meet template
+   * zeros or results that are not stored) and slots [0, ns2) of rows jc .. of the group's templates (zeros past nj rows, past m) */
+  auto stage = [&](unsigned jc, unsigned nj, unsigned ns2) {
+    const unsigned nitems = (7u + nj) * idw;
+    for (unsigned i = tid; i < nitems; i += 256u) {
+      const unsigned r = i / idw, c = i - r * idw;
+      const unsigned y = by0 + jc + r, x = bx0 + 4u * c;
+      uint32_t v = 0;
+      if (y < a.ih && x < a.iw) {
+        const uint8_t *p = a.img + (size_t)y * a.iw + x;
+        if (x + 4u <= a.iw) v = load_u32_unaligned(p) ^ 0x80808080u;
+        else
+          for (unsigned b = 0; x + b < a.iw; b++) v |= (uint32_t)(p[b] ^ 0x80u) << (8 * b);
+      }
+      *(uint32_t *)(limg + (size_t)r * a.istride + 4u * c) = v;
+    }
+    const unsigned nsl = nj * spr, nt16 = 32u * NT * ns2;
+    for (unsigned i = tid; i < nt16; i += 256u) {
+      const unsigned tt = i / ns2, sl = i - tt * ns2, t = tg0 + tt;
+      uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0; /* four scalars: a struct written under a condition lives in scratch memory */
+      if (t < a.m && sl < nsl) {
+        const U4 v = *(const U4 *)(a.bank + ((size_t)t * a.th + jc) * a.rb + 16u * sl);
+        v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
+      }
+      *(U4 *)(ltm + (size_t)tt * a.tstride + 16u * sl) = U4{v0, v1, v2, v3};
+    }
+  };
+  const unsigned wy = (wave >> 1) * 4u, wx = (wave & 1u) * 32u, n = lane & 31u, g = lane >> 5;
+  const unsigned sh = 8u * (n & 3u); /* istride, wx and a slot's column are multiples of 4: the byte phase is the lane's */
+  int32_t acc[NT][4][16];
+#pragma unroll
+  for (unsigned q = 0; q < NT; q++)
+#pragma unroll
+    for (unsigned p = 0; p < 4; p++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[q][p][r] = 0;
+  /* K step k of a band: lane half g takes slot 2 k + g = 16 taps from column c of the band's row j */
+  auto load_step = [&](unsigned k, unsigned j, unsigned c, U4 (&A)[NT], U4 (&B)[4]) {
+#pragma unroll
+    for (unsigned q = 0; q < NT; q++) A[q] = *(const U4 *)(ltm + (size_t)(32u * q + n) * a.tstride + 16u * (2u * k + g));
+#pragma unroll
+    for (unsigned p = 0; p < 4; p++) {
+      const uint32_t *ip = (const uint32_t *)(limg + (size_t)(wy + p + j) * a.istride + ((wx + n + c) & ~3u));
+      const uint32_t d0 = ip[0], d1 = ip[1], d2 = ip[2], d3 = ip[3], d4 = ip[4];
+      B[p] = U4{alignbit(d1, d0, sh), alignbit(d2, d1, sh), alignbit(d3, d2, sh), alignbit(d4, d3, sh)};
+    }
+  };
+  for (unsigned jc = 0; jc < a.th; jc += a.band) { /* block-uniform */
+    const unsigned nj = a.th - jc < a.band ? a.th - jc : a.band;
+    const unsigned ns2 = (nj * spr + 1u) & ~1u, nk = ns2 / 2u;
+    if (jc) __syncthreads(); /* the previous band's operand reads are done */
+    stage(jc, nj, ns2);
+    __syncthreads();
+    unsigned j = spr == 1u ? g : 0u, c = spr == 1u ? 0u : 16u * g; /* slot g */
+    U4 Ac[NT], Bc[4], An[NT], Bn[4];
+    load_step(0, j, c, Ac, Bc);
+    for (unsigned k = 0; k < nk; k++) {
+      /* no branch inside a trip: the last one requests its own operands again (and drops them) */
+      unsigned jn = j, cn = c + 32u; /* two slots on: at most two rows on */
+      if (cn >= a.rb) cn -= a.rb, jn++;
+      if (cn >= a.rb) cn -= a.rb, jn++;
+      const bool more = k + 1u < nk;
+      jn = more ? jn : j, cn = more ? cn : c;
+      load_step(more ? k + 1u : k, jn, cn, An, Bn);
+#pragma unroll
+      for (unsigned q = 0; q < NT; q++)
+#pragma unroll
+        for (unsigned p = 0; p < 4; p++) mfma_i32_32x32x32_i8(Ac[q], Bc[p], acc[q][p]);
+#pragma unroll
+      for (unsigned q = 0; q < NT; q++) Ac[q] = An[q];
+#pragma unroll
+      for (unsigned p = 0; p < 4; p++) Bc[p] = Bn[p];
+      j = jn, c = cn;
+    }
+  }
+  /* results: register r of lane (n, g) of tile (q, p) is template tg0 + 32 q + (r & 3) + 8 (r >> 2) + 4 g at position
+   * (bx0 + wx + n, by0 + wy + p); score = floor(SSD / (255 taps)) as in k_match_template_mfma */
+  const unsigned dv = 255u * a.tw * a.th;
+  const float inv = 1.0f / (float)dv;
+  const unsigned x = bx0 + wx + n;
+  const size_t rbm = (size_t)a.rw * a.rh;
+  unsigned sv[4];
+#pragma unroll
+  for (unsigned p = 0; p < 4; p++) sv[p] = (x < a.rw && by0 + wy + p < a.rh) ? a.s2[(size_t)(by0 + wy + p) * a.rw + x] : 0u;
+  unsigned long long *red = (unsigned long long *)smem; /* locate: [wave][32 NT templates], over the image rows */
+  if (!a.result) __syncthreads();                       /* block-uniform: every wave is done with the operands */
+#pragma unroll
+  for (unsigned q = 0; q < NT; q++) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const unsigned tl = 32u * q + (unsigned)((r & 3) + 8 * (r >> 2)) + 4u * g, t = tg0 + tl;
+      const unsigned tsq = t < a.m ? a.tsq[t] : 0u;
+      unsigned long long best = 0; /* the largest score at the lowest raster index of this lane's four results */
+#pragma unroll
+      for (unsigned p = 0; p < 4; p++) {
+        const unsigned y = by0 + wy + p;
+        if (t < a.m && x < a.rw && y < a.rh) {
+          const unsigned ssd = sv[p] + tsq - 2u * (unsigned)acc[q][p][r]; /* >= 0 and < 2^32: modular arithmetic is exact */
+          unsigned qq = (unsigned)((float)ssd * inv);
+          const int rem = (int)(ssd - qq * dv); /* |true quotient - qq| <= 1, so the remainder fits */
+          if (rem < 0) qq--;
+          else if ((unsigned)rem >= dv) qq++;
+          const unsigned score = qq < 255u ? qq : 255u;
+          if (a.result) a.result[((size_t)fl * a.m + t) * rbm + (size_t)y * a.rw + x] = (uint8_t)(255u - score); /* block-uniform */
+          else {
+            const unsigned long long key = ((unsigned long long)(255u - score) << 32) | (0xffffffffu - (y * a.rw + x));
+            best = key > best ? key : best;
+          }
+        }
+      }
+      if (!a.result) { /* every lane of the wave is here: the 32 lanes of a half hold one template */
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) {
+          const uint32_t lo = shfl((uint32_t)best, (int)(lane ^ (unsigned)d)), hi = shfl((uint32_t)(best >> 32), (int)(lane ^ (unsigned)d));
+          const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+          best = o > best ? o : best;
+        }
+        if (n == 0) red[wave * (32u * NT) + tl] = best;
+      }
+    }
+  }
+  if (!a.result) {
+    __syncthreads();
+    if (tid < 32u * NT && tg0 + tid < a.m) {
+      unsigned long long best = red[tid];
+#pragma unroll
+      for (unsigned w = 1; w < 4; w++) best = red[w * (32u * NT) + tid] > best ? red[w * (32u * NT) + tid] : best;
+      unsigned long long *word = a.keys + (size_t)(tg0 + tid) * a.kstride + fl;
+      /* the maximum over all blocks is the map's first maximum whatever order they arrive in; a block that saw only zeros, or
+       * no more than the word holds, leaves it alone */
+      if ((best >> 32) && best > *(volatile unsigned long long *)word) atomicMax(word, best);
+    }
+  }
+}
+
+/* keys[t * n + f] (value << 32 | ~(y * rw + x); 0 in the high half: no non-zero value seen) -> best[f * m + t] = {x, y},
+ * score[f * m + t] (may be NULL) and winner[f] (may be NULL): the template with the highest score, the lowest index on ties.
+ * grid ceil(n m / 256), block 256 */
+__global__ __launch_bounds__(256) void k_tm_bank_best(const unsigned long long *keys, unsigned n, unsigned m, unsigned rw, unsigned *best,
+                                                      uint8_t *score, unsigned *winner) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n * m) return;
+  const unsigned f = i / m, t = i - f * m;
+  const unsigned long long key = keys[(size_t)t * n + f];
+  const unsigned v = (unsigned)(key >> 32), idx = 0xffffffffu - (unsigned)key;
+  best[2u * i] = v ? idx % rw : 0u, best[2u * i + 1u] = v ? idx / rw : 0u;
+  if (score) score[i] = (uint8_t)v;
+  if (winner && i < n) { /* frame i */
+    unsigned w = 0, top = 0;
+    for (unsigned k = 0; k < m; k++) {
+      const unsigned s = (unsigned)(keys[(size_t)k * n + i] >> 32);
+      if (s > top) top = s, w = k;
+    }
+    winner[i] = w;
   }
 }
 

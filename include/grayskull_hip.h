@@ -84,8 +84,10 @@ enum gsh_tune_key {
   GSH_TUNE_RETIRED_24 = 24,       /* retired (realigning strip flavour never / always) */
   GSH_TUNE_GEOM_FORM = 25,        /* the resize kernels: 1 gather every tap from global memory (no LDS staging), 2 stage the source
                                      rectangle wherever it fits the LDS, also beyond four source pixels per result pixel */
-  GSH_TUNE_TMATCH_CHUNK = 26      /* most frames per chunk of the template-matching batch entries (0 = by their scratch budget; test
+  GSH_TUNE_TMATCH_CHUNK = 26,     /* most frames per chunk of the template-matching batch entries (0 = by their scratch budget; test
                                      hook: a chunk boundary with three small frames) */
+  GSH_TUNE_TMATCH_BANK = 27       /* gsh_match_templates_batch / gsh_locate_templates_batch: 0 by rule, 1 always the loop over the
+                                     templates, 2 the bank kernel wherever it is valid; results never depend on it */
 };
 void gsh_tune(int key, int value);
 /* measurement aid for bench.py: while on, gsh_edge_pipeline_batch brackets every launch of its
@@ -328,6 +330,22 @@ void gsh_find_best_match_batch(const uint8_t *result, unsigned rw, unsigned rh, 
 void gsh_locate_template_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
                                const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
                                struct gs_point *best, uint8_t *score);
+/* A BANK of templates: every frame against m templates of one size (a marker dictionary, glyphs, patches cut by
+ * gsh_crop_resize_batch).  Contract as above; n == 0 || m == 0 returns before any check or launch.  GS_ASSERT: non-NULL
+ * pointers, non-zero sizes, tw <= iw, th <= ih.  From a handful of templates (GSH_TUNE_TMATCH_BANK) the cross term of all
+ * templates is ONE matrix product on the matrix cores (positions x templates x taps; templates up to 512 wide and 32768
+ * taps), below that a loop of the single-template launches; either way a frame's window sums are computed once, and the
+ * scratch per frame is the prefix table and ONE plane of window sums whatever m is. */
+/* n frames of iw x ih against a bank of m templates, all tw x th, template t at tmpl + t*tw*th.
+ * result: n*m maps of rw x rh, map (f, t) at result + (f*m + t)*rw*rh, each byte for byte gs_match_template(frame f, template t) */
+void gsh_match_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
+                               const uint8_t *tmpl, unsigned tw, unsigned th, unsigned m, uint8_t *result);
+/* == the above followed by gs_find_best_match on every map, with no caller-visible map:
+ * best[f*m + t], score[f*m + t] (score may be NULL; an all-zero map gives {0,0} / 0);
+ * winner (n entries, may be NULL): per frame the template with the highest score, the lowest index on ties */
+void gsh_locate_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
+                                const uint8_t *tmpl, unsigned tw, unsigned th, unsigned m,
+                                struct gs_point *best, uint8_t *score, unsigned *winner);
 
 /* ---- connected components, blob corners, perspective correction (ref :330, :404, :423) ----------
  * The reference's document-scanner chain (blur -> Otsu threshold -> gs_blobs -> largest blob ->
