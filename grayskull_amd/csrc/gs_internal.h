@@ -68,6 +68,11 @@ void launch_blur_sobel_hist(unsigned radius, dim3 grid, dim3 block, hipStream_t 
                             unsigned *partial);
 void launch_blur_sobel(unsigned radius, dim3 grid, dim3 block, hipStream_t st, uint8_t *dst, const uint8_t *src,
                        unsigned w, unsigned h, unsigned T, size_t frame_bytes, int rg);
+void launch_blur_sobel_codes(unsigned radius, dim3 grid, dim3 block, hipStream_t st, const uint8_t *src, unsigned w, unsigned h,
+                             unsigned T, size_t frame_bytes, unsigned *partial, uint8_t *codes, size_t code_frame_bytes,
+                             unsigned pairs_per_band, const uint8_t *guess);
+void launch_blur_sobel_repair(unsigned radius, dim3 grid, dim3 block, hipStream_t st, uint8_t *dst, const uint8_t *src, unsigned w,
+                              unsigned h, unsigned T, size_t frame_bytes, const uint8_t *guess, const uint8_t *thr);
 /* gs_box.cpp */
 void launch_box(int mode, unsigned ring_radius, dim3 grid, unsigned threads, hipStream_t st, uint8_t *dst, const uint8_t *src, unsigned w,
                 unsigned h, unsigned T, size_t frame_bytes, unsigned r, int c);
@@ -84,11 +89,23 @@ namespace gsi {
 enum Slot { SL_IN = 0, SL_OUT, SL_AUX, SL_AUX2, SL_II, SL_PAD, SL_MASK, SL_CNT, SL_PFX, SL_TOT, SL_PRE,
             SL_HISTP, SL_HIST, SL_THR, SL_KPS, SL_MOM, SL_KIN, SL_DESC, SL_TAB, SL_JUMP, SL_LEV,
             SL_BEST, SL_NZ, SL_ORB_LEVELS, /* per-frame level counts of gsh_orb_extract_pyramid_batch_nostdlib */
-            SL_BLOB_BITS, SL_BLOB_PAR, SL_BLOB_STAT, SL_BLOB_ROW, SL_BLOB_LAB, SL_BLOB_REC, SL_COUNT }; /* gs_blobs.cpp */
+            SL_BLOB_BITS, SL_BLOB_PAR, SL_BLOB_STAT, SL_BLOB_ROW, SL_BLOB_LAB, SL_BLOB_REC, /* gs_blobs.cpp */
+            SL_CODES, /* gsh_edge_pipeline_batch: the per-frame guesses and the ring of edge-code chunk buffers */
+            SL_COUNT };
 
 /* gsh_edge_pipeline_batch: frames per chunk (measured best for 64..512-frame batches of 4K frames:
  * profiles/r01g_chunk_overlap.log) and the most chunks per call */
 constexpr unsigned kChunkFrames = 32, kMaxChunks = 256; /* 8192 frames per call keep the chunk overlap */
+/* the coded chunks of gsh_edge_pipeline_batch.  kCodeGuessLag: how many chunks back a chunk takes its guesses from (key 28:
+ * -2 / -3 force 2 / 1).  One back makes the caller's stream wait for the k_otsu that runs behind the previous fused launch,
+ * a gap of 35 us per chunk where the launches otherwise follow each other at 7 us (3.42 against 3.05 ms per 512-frame step,
+ * profiles/r07a_codes_ab.json); two back, that k_otsu ran under the previous fused launch and the wait is over before it starts.
+ * kCodeRing: code buffers in the ring.  The fused launch of chunk i reuses the buffer of chunk i - kCodeRing, whose expander
+ * precedes the k_otsu of chunk i - kCodeRing + 1 on the side stream; the launch waits for the k_otsu of chunk i - lag, so with
+ * lag < kCodeRing that one wait covers the buffer as well (two buffers would need the expander that ends WITH the previous fused
+ * launch: measured, 16 us between the launches). */
+constexpr unsigned kCodeGuessLag = 2, kCodeRing = 3;
+static_assert(kCodeRing > 2, "lags of 1 and 2 chunks must both be below the ring size (gs_stencil.cpp waits for the guesses only)");
 /* per-(thread, cascade) scan geometry of the last gs_lbp_detect call: the scale list and the
  * per-(scale, classifier) corner offsets on the device.  Lives in the calling thread's context, not
  * in the cascade handle, so threads sharing one handle never touch each other's tables. */
@@ -190,6 +207,9 @@ struct Ctx {
   }
   hipStream_t side = nullptr; /* chunk overlap inside gsh_edge_pipeline_batch */
   hipEvent_t ev_join = nullptr, ev_chunk[kMaxChunks] = {};
+  /* coded chunks, recorded on the side stream behind chunk i's k_otsu: its thresholds and guesses are written (and every
+   * expander of an earlier chunk is done) */
+  hipEvent_t ev_guess[kMaxChunks] = {};
   hipEvent_t ev_switch = nullptr; /* gsh_set_stream: the stream entered waits for what was enqueued on the one left */
   void ensure_side() {
     if (side) return;
@@ -207,6 +227,11 @@ struct Ctx {
     }
     GS_HIP(hipEventCreateWithFlags(&ev_join, order_event_flags()));
     for (auto &e : ev_chunk) GS_HIP(hipEventCreateWithFlags(&e, order_event_flags()));
+  }
+  void ensure_code_events(size_t chunks) { /* created as far as a call needs them */
+    for (size_t i = 0; i < chunks && i < kMaxChunks; i++) {
+      if (!ev_guess[i]) GS_HIP(hipEventCreateWithFlags(&ev_guess[i], order_event_flags()));
+    }
   }
 #endif
 
@@ -281,6 +306,10 @@ struct Ctx {
       (void)hipStreamDestroy(side), (void)hipEventDestroy(ev_join);
       for (auto &e : ev_chunk) (void)hipEventDestroy(e), e = nullptr;
       side = nullptr, ev_join = nullptr;
+    }
+    for (size_t i = 0; i < kMaxChunks; i++) {
+      if (ev_guess[i]) (void)hipEventDestroy(ev_guess[i]);
+      ev_guess[i] = nullptr;
     }
 #endif
     if (own_stream) (void)hipStreamDestroy(stream);

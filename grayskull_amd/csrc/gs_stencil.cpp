@@ -8,6 +8,7 @@
 #include "gs_internal.h"
 
 #include "k_geom.h"
+#include "k_codes.h"
 #include "k_integral.h"
 #include "k_pointwise.h"
 #include "k_resize.h"
@@ -445,7 +446,7 @@ void launch_otsu(const uint8_t *img, unsigned w, unsigned h, unsigned n, unsigne
                  uint8_t *thr) {
   launch_histogram(img, (size_t)(w * h), n, hist);
   for_frames(n, [&](unsigned f0, unsigned nn) {
-    GS_LAUNCH(k_otsu, dim3(nn), dim3(256), 0, ctx().s(), hist + (size_t)f0 * 256, w * h, thr + f0, (const unsigned *)nullptr, 0u, 0u);
+    GS_LAUNCH(k_otsu, dim3(nn), dim3(256), 0, ctx().s(), hist + (size_t)f0 * 256, w * h, thr + f0, (const unsigned *)nullptr, 0u, 0u, (uint8_t *)nullptr, 0);
   });
 }
 
@@ -949,16 +950,95 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
 #endif
       });
     };
-    auto run_rest = [&](hipStream_t on, unsigned f0, unsigned nn) {
+    /* Chunks after the first of a chunked call, radius 2 (key 28: -1 never): the coded path.  Chunk 0 runs the byte path
+     * above; its k_otsu also leaves every frame's window base b (k_pointwise.h).  The fused launch of chunk i >= 1 writes
+     * 4-bit codes of the edge values around the guess of frame j of chunk i - lag (the same position in the chunk: video
+     * or tiles change slowly; chunks are `per` frames apart, only the last may be shorter) into a ring of chunk buffers
+     * instead of edge bytes into dst, 0.5 B/px.  Behind the chunk's k_otsu, k_expand_codes (k_codes.h) writes the final
+     * bytes of the frames whose threshold fell into the window (0.5 R + 1 W: 3 B/px instead of 4), and one launch of the
+     * fused kernel's repair mode redoes the others exactly (every block of a frame that hit returns at once).  Guesses
+     * come from this call only; thr, hist and dst never depend on them.  No host read-back, no flags in memory: the
+     * streams are ordered by events alone. */
+    const int tune_codes = g_tune[GSH_TUNE_PIPELINE_CODES];
+    const bool chunked = sizes.size() > 1 && sizes.size() <= kMaxChunks;
+    const bool coded = chunked && radius == 2 && tune_codes != -1;
+    const unsigned lag = tune_codes == -2 ? 2u : tune_codes == -3 ? 1u : kCodeGuessLag;
+    const int force = tune_codes > 0 ? tune_codes : 0;
+    struct CodeGeom { unsigned lanes, ppb, npairs; size_t cfb; }; /* a frame's code plane (CodePairs, k_strip.h) */
+    auto code_geom = [&](const StripCfg &c) {
+      CodeGeom g;
+      g.lanes = c.grid.x * c.block.x, g.ppb = (c.T + 1) / 2;
+      g.npairs = ((h - 2 + c.T - 1) / c.T) * g.ppb;
+      g.cfb = (size_t)g.npairs * g.lanes * 16;
+      GS_ASSERT(g.cfb < 0x7fffffffull);
+      return g;
+    };
+    uint8_t *guess = nullptr, *ring = nullptr;
+    size_t ring_bytes = 0;
+    if (coded) {
+      for (size_t i = 1; i < sizes.size(); i++) ring_bytes = std::max(ring_bytes, code_geom(cfg_for(sizes[i])).cfb * sizes[i]);
+      const size_t gb = ((size_t)n + 255) & ~(size_t)255;
+      guess = (uint8_t *)ctx().scratch(SL_CODES, gb + kCodeRing * ring_bytes);
+      ring = guess + gb;
+    }
+    /* the frame whose guess frame f0 of chunk i takes */
+    auto guess_from = [&](size_t i, unsigned f0) { return f0 - per * (unsigned)std::min<size_t>(lag, i); };
+    auto run_fused_codes = [&](hipStream_t on, size_t i, unsigned f0, unsigned nn) {
+      const StripCfg c = cfg_for(nn);
+      const CodeGeom cg = code_geom(c);
+      uint8_t *buf = ring + (i % kCodeRing) * ring_bytes;
+      const uint8_t *gs = guess + guess_from(i, f0);
+      for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
+#ifndef GS_EMU
+        ctx().prof_mark(0, on);
+#endif
+        launch_blur_sobel_codes(radius, dim3(c.grid.x, c.grid.y, m), c.block, on, src + fb * g0, w, h, c.T, fb,
+                                partial + (size_t)g0 * bpf_max * 256, buf + cg.cfb * (g0 - f0), cg.cfb, cg.ppb, gs + (g0 - f0));
+#ifndef GS_EMU
+        ctx().prof_mark(1, on);
+#endif
+      });
+    };
+    auto run_otsu = [&](hipStream_t on, unsigned f0, unsigned nn) {
       const StripCfg c = cfg_for(nn);
       const unsigned bpf = c.grid.x * c.grid.y;
       for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
         const unsigned *pp = partial + (size_t)g0 * bpf_max * 256;
-        /* the 2w + 2(h-2) frame pixels are 0 in the result and were not counted by the kernel; the threshold pass
-         * below waits for this launch only (k_otsu folds the blocks' partial histograms itself) */
+        /* the 2w + 2(h-2) frame pixels are 0 in the result and were not counted by the kernel; the passes behind it
+         * wait for this launch only (k_otsu folds the blocks' partial histograms itself) */
         GS_LAUNCH(k_otsu, dim3(m), dim3(256), 0, on, hist_scratch + (size_t)g0 * 256, w * h, thr + g0, pp, bpf,
-                  2 * w + 2 * (h - 2));
+                  2 * w + 2 * (h - 2), guess ? guess + g0 : (uint8_t *)nullptr, force);
       });
+    };
+    auto run_expand = [&](hipStream_t on, size_t i, unsigned f0, unsigned nn) {
+      const StripCfg c = cfg_for(nn);
+      const CodeGeom cg = code_geom(c);
+      const uint8_t *buf = ring + (i % kCodeRing) * ring_bytes, *gs = guess + guess_from(i, f0);
+      const unsigned waves = cg.npairs * (cg.lanes / 64), bx = std::max(1u, std::min((waves + 3) / 4, 2048u));
+      for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
+        GS_LAUNCH(k_expand_codes, dim3(bx, m), dim3(256), 0, on, dst + fb * g0, buf + cg.cfb * (g0 - f0), w, h, c.T, fb, cg.cfb, cg.lanes,
+                  cg.ppb, cg.npairs, (const uint8_t *)(thr + g0), gs + (g0 - f0));
+      });
+    };
+    /* Once per call, behind the last chunk: the repair launch over all coded frames (per chunk, the all-exit launch and the
+     * queue gap behind it took 11 of a chunk's 192 us on the side stream, which was as long as the fused launch it runs
+     * under), then their 1-px frames.  Frames with the same guess distance go in one launch: chunks 1 .. lag-1, then the rest */
+    auto run_repair = [&](hipStream_t on) {
+      size_t i = 1;
+      while (i < sizes.size()) {
+        size_t j = i < lag ? i + 1 : sizes.size();
+        const unsigned f0 = per * (unsigned)i, nn = std::min(n, per * (unsigned)j) - f0;
+        const StripCfg c = cfg_for(std::min(nn, per));
+        const uint8_t *gs = guess + guess_from(i, f0);
+        for_frames(f0, nn, kMaxZ, [&](unsigned g0, unsigned m) {
+          launch_blur_sobel_repair(radius, dim3(c.grid.x, c.grid.y, m), c.block, on, dst + fb * g0, src + fb * g0, w, h, c.T, fb,
+                                   gs + (g0 - f0), thr + g0);
+        });
+        i = j;
+      }
+      zero_frame(on, per, n - per); /* behind the passes that write whole strips, as on the byte path */
+    };
+    auto run_threshold = [&](hipStream_t on, unsigned f0, unsigned nn) {
       launch_threshold(dst + fb * f0, fb, nn, thr + f0, 0, on);
       /* gs_sobel ran "into a zeroed image": only its 1-px frame is left to zero.  AFTER the threshold pass (which
        * turns whatever the fused kernel left there into 0 / 255): the frame is then 0 either way, and the
@@ -966,33 +1046,59 @@ void gsh_edge_pipeline_batch(uint8_t *dst, uint8_t *tmp, const uint8_t *src, uns
       zero_frame(on, f0, nn);
     };
 #ifdef GS_EMU
-    const bool split = false;
-#else
-    const bool split = sizes.size() > 1 && sizes.size() <= kMaxChunks;
-#endif
-    if (!split) {
+    /* one stream: the coded path chunk after chunk, so that its logic is tested without a GPU; else one launch */
+    if (!coded) {
       run_fused(st, 0, n);
-      run_rest(st, 0, n);
+      run_otsu(st, 0, n);
+      run_threshold(st, 0, n);
       return;
     }
-#ifndef GS_EMU
+    unsigned f0 = 0;
+    for (size_t i = 0; i < sizes.size(); f0 += sizes[i], i++) {
+      const unsigned nn = sizes[i];
+      if (i == 0) run_fused(st, f0, nn), run_otsu(st, f0, nn), run_threshold(st, f0, nn);
+      else run_fused_codes(st, i, f0, nn), run_otsu(st, f0, nn), run_expand(st, i, f0, nn);
+    }
+    run_repair(st);
+#else
+    if (!chunked) {
+      run_fused(st, 0, n);
+      run_otsu(st, 0, n);
+      run_threshold(st, 0, n);
+      return;
+    }
     Ctx &cx = ctx();
     cx.ensure_side();
+    if (coded) cx.ensure_code_events(sizes.size());
     unsigned f0 = 0;
-    for (size_t i = 0; i < sizes.size(); i++) {
+    size_t waited = kMaxChunks; /* the chunk whose ev_guess the caller's stream waited for last */
+    for (size_t i = 0; i < sizes.size(); f0 += sizes[i], i++) {
       const unsigned nn = sizes[i];
-      run_fused(st, f0, nn);
-      if (i + 1 == sizes.size()) { /* last chunk: nothing left to hide it under; rejoin the caller's stream */
+      const bool codes = coded && i >= 1, last = i + 1 == sizes.size();
+      if (codes) {
+        /* the guesses are written; the same wait covers the code buffer's last reader (kCodeRing, gs_internal.h) */
+        const size_t from = i - std::min<size_t>(lag, i);
+        if (from != waited) GS_HIP(hipStreamWaitEvent(st, cx.ev_guess[from], 0));
+        waited = from;
+        run_fused_codes(st, i, f0, nn);
+      } else {
+        run_fused(st, f0, nn);
+      }
+      hipStream_t on = cx.side;
+      if (last) { /* last chunk: nothing left to hide it under; rejoin the caller's stream */
         GS_HIP(hipEventRecord(cx.ev_join, cx.side));
         GS_HIP(hipStreamWaitEvent(st, cx.ev_join, 0));
-        run_rest(st, f0, nn);
+        on = st;
       } else {
         GS_HIP(hipEventRecord(cx.ev_chunk[i], st));
         GS_HIP(hipStreamWaitEvent(cx.side, cx.ev_chunk[i], 0));
-        run_rest(cx.side, f0, nn);
       }
-      f0 += nn;
+      run_otsu(on, f0, nn);
+      if (coded && !last) GS_HIP(hipEventRecord(cx.ev_guess[i], on));
+      if (codes) run_expand(on, i, f0, nn);
+      else run_threshold(on, f0, nn);
     }
+    if (coded) run_repair(st);
 #endif
     return;
   }

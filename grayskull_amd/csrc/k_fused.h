@@ -65,14 +65,57 @@ GS_DEV void blur_hsum10(const uint32_t (&U)[12], uint32_t (&H)[10]) { /* pairs =
 /* RAGGED (w % 16 != 0, without the histogram half): the strips of k_strip.h with the tail strip anchored at w - 16.  The lane
  * left of the tail lane may own pixels -- its own last R and the two it blurs for its right neighbour's sobel taps -- that are
  * less than R columns from the right edge, so the right-hand divisors are chosen per lane from the distance to the edge. */
+/* MODE: what leaves the kernel per pixel.
+ *   kFusedBytes   the sobel byte, to dst (1 B/px written).
+ *   kFusedCodes   (HIST, RG 0, even unroll period) a 4-bit code of the sobel value e relative to a per-frame guess of the
+ *                 Otsu threshold that the histogram of this very launch will give: c = min(max(e - b, 0), 15) with
+ *                 b = aux.guess[frame] (already clamped by its writer: clamp(guess, 8, 248) - 8).  For the frame's true
+ *                 threshold t with b <= t <= b + 14 (a hit), e > t <=> c > t - b, so k_expand_codes (k_codes.h) writes the
+ *                 final 0 / 255 bytes from the codes alone: 0.5 B/px written here, 0.5 read + 1 written there, instead of
+ *                 1 + 1 + 1.  Two rows' codes of a lane leave as one 16-byte store (CodePairs, k_strip.h) into aux.codes;
+ *                 dst is not touched.  The histogram half is the byte mode's, so hist and thr do not depend on the guess.
+ *   kFusedRepair  (no histogram) the frames whose guess missed (t outside [b, b + 14]), once t is known: the byte mode with
+ *                 the threshold applied in registers, final bytes to dst.  Every block of a frame that hit returns before its
+ *                 first load.
+ * Ordering between the launches is stream order and events only (gs_stencil.cpp). */
+enum { kFusedBytes = 0, kFusedCodes = 1, kFusedRepair = 2 };
+struct FusedAux {
+  uint8_t *codes = nullptr;       /* kFusedCodes: the launch's code planes, code_frame_bytes apart */
+  size_t code_frame_bytes = 0;    /* bands * pairs_per_band * pair_bytes */
+  unsigned pair_bytes = 0;        /* 16 * (gridDim.x * blockDim.x): one row pair of codes */
+  unsigned pairs_per_band = 0;    /* (T + 1) / 2 */
+  const uint8_t *guess = nullptr; /* per frame of the launch: b */
+  const uint8_t *thr = nullptr;   /* kFusedRepair: per frame of the launch: t */
+};
+GS_DEV bool code_hit(unsigned t, unsigned b) { return b <= t && t <= b + 14u; }
+struct ThresholdFin { /* Fin functor of strip_rows: x > t ? 255 : 0 on the row about to be stored */
+  static constexpr bool kPairs = false;
+  uint32_t trep;
+  template <int> GS_DEV void put(int, int, const U4 &) {}
+  GS_DEV void prefetch(int) {}
+  GS_DEV U4 operator()(const U4 &o, int) const {
+    return U4{swar_gt_u8(o.x, trep), swar_gt_u8(o.y, trep), swar_gt_u8(o.z, trep), swar_gt_u8(o.w, trep)};
+  }
+};
+struct FusedNoAux {}; /* the byte mode's: an empty argument, nothing in the kernel's argument segment */
+template <int MODE> struct FusedAuxFor { typedef FusedAux type; };
+template <> struct FusedAuxFor<kFusedBytes> { typedef FusedNoAux type; };
 /* MINW: waves per SIMD the register allocation has to leave room for (__launch_bounds__' second argument) */
-template <int R, bool HIST = true, int RG = 0, int MINW = 1>
+/* One __global__ template for all modes (not a shared device function behind three kernels: inlined that way, hipcc no longer
+ * folds blockDim into the kernel's known block size and the byte mode's prologue and register count change). */
+template <int R, bool HIST = true, int RG = 0, int MINW = 1, int MODE = kFusedBytes>
 __global__ __launch_bounds__(256, MINW) GS_FUSED_VGPR_ATTR void k_blur_sobel_hist16(uint8_t *dst, const uint8_t *src,
                                                            unsigned w, unsigned h, unsigned T,
-                                                           size_t frame_bytes, unsigned *partial) {
+                                                           size_t frame_bytes, unsigned *partial,
+                                                           typename FusedAuxFor<MODE>::type aux) {
   constexpr bool RAGGED = RG != 0;
   static_assert(!(HIST && RAGGED), "ragged rows take the histogram as a separate pass");
+  static_assert(MODE != kFusedCodes || (HIST && R <= 2), "codes: with the histogram half, even unroll period");
+  static_assert(MODE != kFusedRepair || (!HIST && !RAGGED), "repair: the byte mode without the histogram half");
   constexpr int N = 2 * R + 1;
+  if constexpr (MODE == kFusedRepair) {
+    if (code_hit(aux.thr[blockIdx.z], aux.guess[blockIdx.z])) return; /* wave-uniform (scalar loads); no barrier in this mode */
+  }
   __shared__ unsigned lh[HIST ? 256 * 32 : 1];
   const unsigned tid = threadIdx.y * blockDim.x + threadIdx.x, copy = tid & 31u;
   if constexpr (HIST) {
@@ -180,7 +223,9 @@ __global__ __launch_bounds__(256, MINW) GS_FUSED_VGPR_ATTR void k_blur_sobel_his
       lds_add_through(lh, mad_u32_u16_hi(Mp[k], 128u, cb), inc, through);
     };
 
-    strip_rows<NS, false, /*EXITS=*/false>(S, y0, nrows, R + 1, S.load(y0 + R + 1), [&](auto I, int i, const uint32_t(&U)[12]) {
+    uint32_t brep = 0; /* kFusedCodes: b in both halves */
+    if constexpr (MODE == kFusedCodes) brep = (uint32_t)aux.guess[blockIdx.z] * 0x10001u;
+    auto body = [&](auto I, int i, const uint32_t(&U)[12]) {
       /* iteration I, SPARE: slot I+1 is free (its row left last iteration), slot I+2 holds the
        * oldest row; otherwise the new row replaces the oldest (slot I+1) */
       constexpr int fr = (decltype(I)::value + 1) % NS, old = (decltype(I)::value + 1 + P0) % NS;
@@ -212,8 +257,25 @@ __global__ __launch_bounds__(256, MINW) GS_FUSED_VGPR_ATTR void k_blur_sobel_his
         for (int k = 0; k < 8; k++) Mp[k] = M[k];
         livep = i < nrows ? 1u : 0u; /* wave-uniform: rows past the band end are dropped */
       }
+      if constexpr (MODE == kFusedCodes) { /* M: the 16 values e as u16 pairs (px 2k, 2k+1) */
+        uint32_t c[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) c[k] = pk_min_u16(pk_subsat_u16(M[k], brep), 0x000f000fu);
+        /* nibbles of a dword, low to high: px 0, 2, 4, 6, 1, 3, 5, 7 of its eight (expand_codes8 undoes it) */
+        o = U4{c[0] | (c[1] << 4) | (c[2] << 8) | (c[3] << 12), c[4] | (c[5] << 4) | (c[6] << 8) | (c[7] << 12), 0u, 0u};
+      }
       return o;
-    });
+    };
+    const RawRow first_raw = S.load(y0 + R + 1);
+    if constexpr (MODE == kFusedCodes) {
+      CodePairs cp{make_buf(aux.codes + (size_t)blockIdx.z * aux.code_frame_bytes, aux.code_frame_bytes),
+                   inimg ? S.gid * 16u : kOOB, aux.pair_bytes, S.band * aux.pairs_per_band * aux.pair_bytes};
+      strip_rows<NS, false, /*EXITS=*/false>(S, y0, nrows, R + 1, first_raw, body, cp);
+    } else if constexpr (MODE == kFusedRepair) {
+      strip_rows<NS, false, /*EXITS=*/false>(S, y0, nrows, R + 1, first_raw, body, ThresholdFin{(uint32_t)aux.thr[blockIdx.z] * 0x01010101u});
+    } else {
+      strip_rows<NS, false, /*EXITS=*/false>(S, y0, nrows, R + 1, first_raw, body);
+    }
     if constexpr (HIST) { /* the last row */
       uint32_t t = 0;
 #pragma unroll

@@ -25,15 +25,6 @@ __host__ __device__ inline Chunking make_chunking(const void *base, size_t n) {
   return c;
 }
 
-/* per-byte x > t ? 0xff : 0 on four bytes at once (SWAR, no cross-byte carries) */
-GS_DEV uint32_t swar_gt_u8(uint32_t x, uint32_t trep) {
-  const uint32_t Hb = 0x80808080u;
-  uint32_t d = (trep | Hb) - (x & ~Hb);                  /* bit7 = (t&0x7f) >= (x&0x7f) */
-  uint32_t ge = ((trep & ~x) | (~(trep ^ x) & d)) & Hb;  /* bit7 = t >= x */
-  uint32_t gt = ~ge & Hb;                                /* bit7 = x > t  */
-  return (gt >> 7) * 0xffu;
-}
-
 /* ref :225-228, in place.  grid (blocks, n frames); thr_dev (per-frame) overrides thr_const; thr_off is added to a
  * per-frame threshold and the sum converted the way C passes an int to a uint8_t parameter (250 + 10 -> 4) */
 __global__ __launch_bounds__(256) void k_threshold(uint8_t *img, size_t frame_bytes,
@@ -179,8 +170,12 @@ __global__ __launch_bounds__(256) void k_hist_reduce(const unsigned *partial, un
 /* partial != nullptr: the histogram is first folded from `bpf` per-block partial histograms (what k_hist_reduce
  * does, saved as a launch: the pipeline's threshold pass waits for this kernel) and written to `hist` as well;
  * extra0 = pixels known to be 0 that no block counted. */
+/* guess != nullptr (the coded edge pipeline, gs_stencil.cpp): the frame's threshold -- or force - 1 where force > 0, the
+ * test hook -- also leaves as the base b = clamp(., 8, 248) - 8 of the 15-level window a later frame's edge codes are
+ * written against (k_fused.h); clamped here, once, for the code's writer and its readers. */
 __global__ __launch_bounds__(256) void k_otsu(unsigned *hist, unsigned npix, uint8_t *thr,
-                                              const unsigned *partial = nullptr, unsigned bpf = 0, unsigned extra0 = 0) {
+                                              const unsigned *partial = nullptr, unsigned bpf = 0, unsigned extra0 = 0,
+                                              uint8_t *guess = nullptr, int force = 0) {
 #ifndef GS_EMU
 #pragma clang fp contract(off)
 #endif
@@ -247,7 +242,12 @@ __global__ __launch_bounds__(256) void k_otsu(unsigned *hist, unsigned npix, uin
   if (t == 0) {
     for (int k = 1; k < 4; k++)
       if (bv[k] > v || (bv[k] == v && bt[k] < a)) v = bv[k], a = bt[k];
-    thr[blockIdx.x] = (uint8_t)(v > -1.0f ? a : 0u);
+    const unsigned tv = v > -1.0f ? a : 0u;
+    thr[blockIdx.x] = (uint8_t)tv;
+    if (guess) {
+      const unsigned g = force > 0 ? (unsigned)(force - 1) & 0xffu : tv;
+      guess[blockIdx.x] = (uint8_t)((g < 8u ? 8u : g > 248u ? 248u : g) - 8u);
+    }
   }
 }
 

@@ -219,8 +219,37 @@ template <bool INVERT = false, int RG = 0> struct Strip {
  * s_waitcnt at the top of the next row finds them (nearly) complete.  RING rows are unrolled
  * so the vertical window is indexed at compile time. */
 struct NoFin {
+  static constexpr bool kPairs = false; /* true: rows leave in pairs through put() (CodePairs), S.store is not used */
+  template <int> GS_DEV void put(int, int, const U4 &) {}
   GS_DEV U4 operator()(const U4 &o, int) const { return o; } /* called right before row y's store */
   GS_DEV void prefetch(int) {}                              /* called when row y's loads issue   */
+};
+/* Store policy of strip_rows for results of 8 bytes per lane and row (the 4-bit edge codes of k_fused.h's coded mode):
+ * gfx950 serves 8-byte accesses at 0.54-0.70 of the 16-byte rate, so a lane keeps the 8 bytes of an even row of its band
+ * and stores them together with the next row's as ONE 16-byte store, every second iteration.  The unroll period is even
+ * and whole groups run (EXITS = false), so which half a row fills is known at compile time (PAR, the parity of the
+ * iteration) and nothing moves between registers.  Layout, private to the writer and its reader (k_codes.h): pair p of
+ * band b at byte (b * pairs_per_band + p) * pair_bytes + 16 * strip, pair_bytes = 16 * lanes placed per row -- a wave's
+ * store is 1 KiB contiguous.  A band with an odd row count ends with a pair whose second half is junk. */
+struct CodePairs {
+  static constexpr bool kPairs = true;
+  BufRsrc buf;
+  uint32_t lane_off;   /* 16 * strip, kOOB outside the image */
+  uint32_t pair_bytes; /* wave-uniform */
+  uint32_t first;      /* byte offset of the band's pair 0, wave-uniform */
+  U4 acc{0, 0, 0, 0};
+  GS_DEV void prefetch(int) {}
+  GS_DEV U4 operator()(const U4 &o, int) const { return o; } /* the per-row store is not used */
+  /* called in iteration i (parity PAR) with row i-1's codes in o.x, o.y, before row i is computed */
+  template <int PAR> GS_DEV void put(int i, int nrows, const U4 &o) {
+    if constexpr (PAR != 0) {
+      acc.x = o.x, acc.y = o.y; /* row i-1 is even: first half */
+    } else {
+      acc.z = o.x, acc.w = o.y; /* rows i-2, i-1 */
+      const bool ok = i > 0 && i - 2 < nrows; /* wave-uniform: the pair holds at least one row of the band */
+      buf_store16(buf, (ok ? first + (uint32_t)((i - 2) >> 1) * pair_bytes : kRowOOB) + lane_off, acc);
+    }
+  }
 };
 /* EXITS: leave the unrolled group at the first row >= nrows (true), or always run whole groups of
  * RING rows (false): then the group is one basic block -- register rotation resolves at compile
@@ -247,7 +276,8 @@ GS_DEV void strip_rows(const Strip<INVERT, RG> &S, int y0, int nrows, int lead, 
       if constexpr (!EXITS) sched_fence(); /* the next row's unpack (= its vmcnt wait) stays down here */
       uint32_t U[12];
       S.unpack(raw, U);
-      S.store(y0 + i - 1, i > 0 && i <= nrows, fin(o_prev, y0 + i - 1));
+      if constexpr (Fin::kPairs) fin.template put<decltype(I)::value & 1>(i, nrows, o_prev);
+      else S.store(y0 + i - 1, i > 0 && i <= nrows, fin(o_prev, y0 + i - 1));
 #if GS_STRIP_PF == 2
       raw = raw2, raw2 = S.load(y0 + i + lead + 2);
 #else
@@ -258,7 +288,10 @@ GS_DEV void strip_rows(const Strip<INVERT, RG> &S, int y0, int nrows, int lead, 
       o_prev = body(I, i, U);
     });
   }
-  if constexpr (EXITS) S.store(y0 + nrows - 1, nrows > 0, fin(o_prev, y0 + nrows - 1));
+  if constexpr (Fin::kPairs) {
+    static_assert(!Fin::kPairs || (!EXITS && RING % 2 == 0), "row pairs need whole groups of an even number of rows");
+    fin.template put<0>(base, nrows, o_prev);
+  } else if constexpr (EXITS) S.store(y0 + nrows - 1, nrows > 0, fin(o_prev, y0 + nrows - 1));
   else S.store(y0 + base - 1, base == nrows && nrows > 0, fin(o_prev, y0 + base - 1));
 }
 
@@ -283,6 +316,8 @@ GS_DEV void sobel_h1(const uint32_t (&U)[12], const uint32_t (&A)[10], uint32_t 
 }
 
 struct SobelKeepCols { /* Fin functor of strip_rows */
+  static constexpr bool kPairs = false;
+  template <int> GS_DEV void put(int, int, const U4 &) {}
   BufRsrc dst;
   unsigned w, x0;
   bool first, last;

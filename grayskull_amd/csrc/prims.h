@@ -484,6 +484,14 @@ GS_DEV uint32_t sub2(uint32_t a, uint32_t b) { return pk_sub_u16(a, b); }
 #endif
 /* |a - b| per field for unsigned fields: max - min (the difference cannot borrow) */
 GS_DEV uint32_t absdiff2(uint32_t a, uint32_t b) { return sub2(pk_max_u16(a, b), pk_min_u16(a, b)); }
+/* per-byte x > t ? 0xff : 0 on four bytes at once (SWAR, no cross-byte carries); trep = t in every byte */
+GS_DEV uint32_t swar_gt_u8(uint32_t x, uint32_t trep) {
+  const uint32_t Hb = 0x80808080u;
+  uint32_t d = (trep | Hb) - (x & ~Hb);                  /* bit7 = (t&0x7f) >= (x&0x7f) */
+  uint32_t ge = ((trep & ~x) | (~(trep ^ x) & d)) & Hb;  /* bit7 = t >= x */
+  uint32_t gt = ~ge & Hb;                                /* bit7 = x > t  */
+  return (gt >> 7) * 0xffu;
+}
 GS_DEV unsigned umin(unsigned a, unsigned b) { return a < b ? a : b; }
 GS_DEV unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
 /* low 32 bits of the product of the operands' low 24 bits: v_mul_u32_u24, a full-rate instruction (v_mul_lo_u32 runs at a quarter) */

@@ -86,8 +86,15 @@ enum gsh_tune_key {
                                      rectangle wherever it fits the LDS, also beyond four source pixels per result pixel */
   GSH_TUNE_TMATCH_CHUNK = 26,     /* most frames per chunk of the template-matching batch entries (0 = by their scratch budget; test
                                      hook: a chunk boundary with three small frames) */
-  GSH_TUNE_TMATCH_BANK = 27       /* gsh_match_templates_batch / gsh_locate_templates_batch: 0 by rule, 1 always the loop over the
+  GSH_TUNE_TMATCH_BANK = 27,      /* gsh_match_templates_batch / gsh_locate_templates_batch: 0 by rule, 1 always the loop over the
                                      templates, 2 the bank kernel wherever it is valid; results never depend on it */
+  GSH_TUNE_PIPELINE_CODES = 28    /* gsh_edge_pipeline_batch, the chunks after the first of a call that is cut into chunks (radius 2):
+                                     0 by rule -- 4-bit edge codes around a guess of each frame's Otsu threshold, taken from the
+                                     frame at the same place two chunks back (chunk 1: one back), expanded by a second pass; a
+                                     frame whose guess missed is redone exactly --, -1 never (every chunk writes edge bytes and
+                                     thresholds them in place), -2 / -3 the guess from two chunks / one chunk back, v >= 1 every
+                                     guess forced to v - 1 (test hook: window edges and misses on small inputs); results never
+                                     depend on it */
 };
 void gsh_tune(int key, int value);
 /* measurement aid for bench.py: while on, gsh_edge_pipeline_batch brackets every launch of its
