@@ -144,6 +144,10 @@ _SIGS = {
     "gsh_orb_pyramid_batch_buffer_bytes": (C.c_size_t, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "gsh_orb_extract_pyramid_batch_nostdlib": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_orb_extract_pyramid_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
+    "gsh_orb_pyramid_batch_times": (None, [C.POINTER(C.c_double)]),
+    "gsh_orb_pyramid_buffer_fill_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "gsh_match_orb_dev": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p,
                                  C.c_void_p, C.c_uint, C.c_float]),
     "gsh_match_orb_batch": (None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint,
@@ -578,6 +582,26 @@ class Grayskull:
         n, h, w = self._nhw(imgs)
         self.c.gsh_orb_extract_pyramid_batch_nostdlib(_ptr(imgs), w, h, n, _ptr(buffer), _ptr(kps), _ptr(counts),
                                                       _ptr(level_counts), nkps, threshold, n_levels)
+
+    def orb_extract_pyramid_batch(self, imgs, buffer, kps, counts, nkps, threshold, n_levels, level_counts=None):
+        """pyramid ORB of the reference's default build (nanomagick.c:245-290, glibc trig on the host): the arguments of
+        orb_extract_pyramid_batch_nostdlib, device tensors; the records stay on the device, the call blocks for its one
+        host round trip"""
+        n, h, w = self._nhw(imgs)
+        self.c.gsh_orb_extract_pyramid_batch(_ptr(imgs), w, h, n, _ptr(buffer), _ptr(kps), _ptr(counts),
+                                             _ptr(level_counts), nkps, threshold, n_levels)
+
+    def orb_pyramid_batch_times(self):
+        """ms of the last orb_extract_pyramid_batch call under profile(True): device before, copy down, host trig, copy up,
+        device after"""
+        ms = (C.c_double * 5)()
+        self.c.gsh_orb_pyramid_batch_times(ms)
+        return list(ms)
+
+    def orb_pyramid_buffer_fill_batch(self, buffer, single, w, h, n_levels, n):
+        """gsh_orb_pyramid_buffer_fill_batch: every plane of the n frames of the batch buffer = that plane of `single`, one
+        frame's buffer (orb_pyramid_buffer_bytes); flat uint8 device buffers"""
+        self.c.gsh_orb_pyramid_buffer_fill_batch(_ptr(buffer), _ptr(single), w, h, n_levels, n)
 
     def match_orb_dev(self, k1, n1, k2, n2, matches, count, max_matches, max_distance):
         self.c.gsh_match_orb_dev(_ptr(k1), n1, _ptr(k2), n2, _ptr(matches), _ptr(count),

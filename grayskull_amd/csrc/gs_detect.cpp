@@ -7,6 +7,8 @@
 #include "gs_internal.h"
 #include <pthread.h>
 
+#include <chrono>
+
 #include "k_fast.h"
 #include "k_fast_nms.h"
 #include "k_lbp.h"
@@ -697,6 +699,158 @@ void orb_extract_levels(OrbLevel *L, unsigned nl, unsigned threshold) {
   for (unsigned l = 0; l < nl; l++) L[l].got = J[l].got;
 }
 
+/* extract_pyramid_orb_nm (ref examples/nanomagick/nanomagick.c:245-290) for n frames: the body of
+ * gsh_orb_extract_pyramid_batch_nostdlib and, with `libm`, of gsh_orb_extract_pyramid_batch.  Arguments checked by the caller,
+ * n > 0.  Both flavours: the level planes in one launch, then per level FAST -> k_orb_select_level.  The device-trig flavour
+ * describes each level right behind its selection (k_orb_describe_level).  The libm flavour leaves the records undescribed
+ * until every level of every frame is selected, then: k_orb_moments_levels, one copy of the moments and the counts to the
+ * host, glibc's atan2f / sinf there (host_pool() from 4096 kept keypoints, as in orb_extract_libm), one copy of
+ * {angle, sin, cos} back, k_orb_brief_levels.  One launch each per kMaxZ frames, ONE round trip per call whatever the split. */
+/* gsh_orb_pyramid_batch_times: where the last libm-flavour call of this thread spent its time, taken only under
+ * gsh_profile(1) (six timing events on the stream and a host clock round the trig; the call then ends synchronised) */
+thread_local double g_orb_times[5] = {0, 0, 0, 0, 0}; /* device before, copy down, host trig, copy up, device after: ms */
+struct OrbTimes {
+#ifndef GS_EMU
+  hipEvent_t e[6] = {};
+  bool on;
+  OrbTimes() : on(ctx().prof_on) {
+    for (auto &x : e)
+      if (on) GS_HIP(hipEventCreateWithFlags(&x, sync_event_flags()));
+  }
+  void mark(int i) {
+    if (on) GS_HIP(hipEventRecord(e[i], ctx().s()));
+  }
+  void done(double host_ms) {
+    if (!on) return;
+    ctx().sync();
+    const int pair[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+    const int slot[4] = {0, 1, 3, 4};
+    for (int i = 0; i < 4; i++) {
+      float ms = 0;
+      GS_HIP(hipEventElapsedTime(&ms, e[pair[i][0]], e[pair[i][1]]));
+      g_orb_times[slot[i]] = ms;
+    }
+    g_orb_times[2] = host_ms;
+  }
+  ~OrbTimes() {
+    for (auto &x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+#else
+  void mark(int) {}
+  void done(double) {}
+#endif
+};
+double host_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+void orb_pyramid_batch(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n, uint8_t *buffer_dev,
+                       struct gs_keypoint *kps_dev, unsigned *counts_dev, unsigned *level_counts_dev, unsigned nkps,
+                       unsigned threshold, unsigned n_levels, bool libm) {
+  hipStream_t st = ctx().s();
+  unsigned lw[4], lh[4];
+  const unsigned L = orb_pyramid_dims(w, h, n_levels, lw, lh);
+  if (level_counts_dev) GS_HIP(hipMemsetAsync(level_counts_dev, 0, (size_t)n * 16, st));
+  if (L == 0 || nkps == 0 || w < 7 || h < 7) { /* the driver's level loop is empty (nanomagick.c:262, :276); gs_fast's loops are (ref :489) */
+    GS_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n * 4, st));
+    return;
+  }
+  OrbTimes times;
+  if (libm) times.mark(0);
+  gsh_pyramid_batch(buffer_dev, img_dev, w, h, n, L);
+  /* plane l of the levels / of the score maps: n frames of lw[l] x lh[l] */
+  const uint8_t *lev[4] = {img_dev, nullptr, nullptr, nullptr};
+  uint8_t *sm[4];
+  size_t fb[4], off = 0;
+  for (unsigned l = 0; l < L; l++) fb[l] = (size_t)lw[l] * lh[l];
+  for (unsigned l = 1; l < L; l++) lev[l] = buffer_dev + off, off += fb[l] * n;
+  for (unsigned l = 0; l < L; l++) sm[l] = buffer_dev + off, off += fb[l] * n;
+  const unsigned per = nkps / L, cap_last = std::min(nkps * 4u, 5000u);
+  /* the libm flavour's level counts live in one array for the whole call: the host half and both of its launches read them */
+  unsigned *lc_all = level_counts_dev;
+  if (!lc_all) {
+    lc_all = (unsigned *)ctx().scratch(SL_ORB_LEVELS, (size_t)(libm ? n : std::min(n, kMaxZ)) * 16);
+    if (libm) GS_HIP(hipMemsetAsync(lc_all, 0, (size_t)n * 16, st));
+  }
+  int *mom = libm ? (int *)ctx().scratch(SL_MOM, (size_t)n * nkps * 8) : nullptr;
+  /* the levels of the launch that starts at frame f0 */
+  auto tab = [&](unsigned f0) {
+    OrbLevelTab T{};
+    for (unsigned l = 0; l < L; l++) T.img[l] = lev[l] + fb[l] * f0, T.fb[l] = fb[l], T.w[l] = lw[l], T.h[l] = lh[l];
+    return T;
+  };
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    unsigned *cand = (unsigned *)ctx().scratch(SL_KPS, (size_t)nn * cap_last * 48 + 16); /* the last level's: the largest */
+    unsigned *cnt = (unsigned *)ctx().scratch(SL_TOT, (size_t)nn * 4 + 16);
+    unsigned *lc = level_counts_dev || libm ? lc_all + 4 * (size_t)f0 : lc_all;
+    if (!level_counts_dev && !libm) GS_HIP(hipMemsetAsync(lc, 0, (size_t)nn * 16, st));
+    unsigned *out = (unsigned *)kps_dev + (size_t)f0 * nkps * 12;
+    for (unsigned l = 0; l < L; l++) {
+      const bool last = l + 1 == L;
+      if (!last && per == 0) continue; /* level_nkps == 0 (nanomagick.c:276): the level's score maps stay as they are */
+      const unsigned quota = last ? nkps : per; /* the last level's: an upper bound, k_orb_select_level has the frame's own */
+      const unsigned cap = std::min(quota * 4u, 5000u);
+      launch_fast(lev[l] + fb[l] * f0, sm[l] + fb[l] * f0, lw[l], lh[l], nn, cand, cnt, cap, threshold);
+      GS_LAUNCH(k_orb_select_level, dim3(nn), dim3(64), 0, st, (const unsigned *)cand, (const unsigned *)cnt, cap, lw[l], lh[l],
+                nkps, per, l, last ? 1u : 0u, out, lc, counts_dev + f0);
+      if (!libm)
+        GS_LAUNCH(k_orb_describe_level, dim3(quota, nn), dim3(256), 0, st, lev[l] + fb[l] * f0, lw[l], lh[l], fb[l], out,
+                  (const unsigned *)lc, nkps, l);
+    }
+    if (libm)
+      GS_LAUNCH(k_orb_moments_levels, dim3(nkps, nn), dim3(256), 0, st, tab(f0), (const unsigned *)out, (const unsigned *)lc, nkps,
+                mom + (size_t)f0 * nkps * 2);
+  });
+  if (!libm) return;
+  /* the round trip: moments and counts through the pinned staging (Ctx::pinned), one synchronisation */
+  unsigned *hn = (unsigned *)ctx().pinned(Ctx::PIN_A, (size_t)n * 4);
+  int *hm = (int *)ctx().pinned(Ctx::PIN_C, (size_t)n * nkps * 8);
+  times.mark(1);
+  GS_HIP(hipMemcpyAsync(hn, counts_dev, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(hm, mom, (size_t)n * nkps * 8, hipMemcpyDeviceToHost, st));
+  times.mark(2);
+  ctx().sync();
+  const double host_t0 = host_now_ms();
+  /* host half of ref :620 and :626: the angle and the two sines of every kept keypoint, frame by frame */
+  float *ht = (float *)ctx().pinned(Ctx::PIN_D, (size_t)n * nkps * 12);
+  size_t kept_total = 0;
+  for (unsigned f = 0; f < n; f++) kept_total += std::min(hn[f], nkps);
+  if (!kept_total) return;
+  auto do_frames = [&](size_t a, size_t b) {
+    for (size_t f = a; f < b; f++)
+      for (size_t i = f * nkps, e = i + std::min(hn[f], nkps); i < e; i++) {
+        const float angle = atan2f((float)hm[2 * i], (float)hm[2 * i + 1]); /* ref :620, :100 */
+        ht[3 * i] = angle, ht[3 * i + 1] = sinf(angle), ht[3 * i + 2] = sinf((float)(angle + 1.57079f)); /* ref :626 */
+      }
+  };
+  unsigned nthreads = 1;
+  if (kept_total >= 4096 && n > 1)
+    nthreads = (unsigned)std::min<size_t>({HostPool::kMax + 1, std::max(1u, std::thread::hardware_concurrency()), n, kept_total / 1024});
+  if (nthreads > 1) host_pool().run(nthreads, [&](unsigned t) { do_frames((size_t)n * t / nthreads, (size_t)n * (t + 1) / nthreads); });
+  else do_frames(0, n);
+  float *dt = (float *)ctx().scratch(SL_KIN, (size_t)n * nkps * 12);
+  const double host_ms = host_now_ms() - host_t0;
+  times.mark(3);
+  GS_HIP(hipMemcpyAsync(dt, ht, (size_t)n * nkps * 12, hipMemcpyHostToDevice, st));
+  /* `ht` is grow-only pinned staging that the next call writes again.  It is guarded by an EVENT recorded right behind the
+   * copy and waited for before this call returns: the descriptor launches are enqueued meanwhile and stay stream-ordered,
+   * the call does not return while the copy may still read `ht`, and so no later call can write it early.  (The emulator's
+   * copies are done when they return.) */
+#ifndef GS_EMU
+  if (!ctx().ev_pin) GS_HIP(hipEventCreateWithFlags(&ctx().ev_pin, order_event_flags()));
+  GS_HIP(hipEventRecord(ctx().ev_pin, st));
+#endif
+  times.mark(4);
+  for_frames(n, [&](unsigned f0, unsigned nn) {
+    GS_LAUNCH(k_orb_brief_levels, dim3(nkps, nn), dim3(256), 0, st, tab(f0), (unsigned *)kps_dev + (size_t)f0 * nkps * 12,
+              (const unsigned *)(lc_all + 4 * (size_t)f0), nkps, (const float *)(dt + (size_t)f0 * nkps * 3));
+  });
+  times.mark(5);
+#ifndef GS_EMU
+  GS_HIP(hipEventSynchronize(ctx().ev_pin));
+#endif
+  times.done(host_ms);
+}
+
 void launch_match(const uint32_t *k1, unsigned n1, const uint32_t *k2, unsigned n2,
                   unsigned *matches, unsigned *count, unsigned max_matches, float max_distance) {
   hipStream_t st = ctx().s();
@@ -980,40 +1134,43 @@ void gsh_orb_extract_pyramid_batch_nostdlib(const uint8_t *img_dev, unsigned w, 
                                             unsigned n_levels) {
   if (n == 0) return;
   GS_ASSERT(img_dev && buffer_dev && kps_dev && counts_dev && w > 0 && h > 0);
-  hipStream_t st = ctx().s();
+  orb_pyramid_batch(img_dev, w, h, n, buffer_dev, kps_dev, counts_dev, level_counts_dev, nkps, threshold, n_levels, false);
+}
+/* The same for the reference's default build, whose atan2f / sinf are glibc's (ref :100-101) and run on the host as in
+ * orb_extract_libm: FAST and the selection of every level first (the selection needs no trig), then the moments of every
+ * kept keypoint in one launch, ONE round trip for the whole call, and every descriptor in one launch (orb_pyramid_batch). */
+void gsh_orb_extract_pyramid_batch(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n,
+                                   uint8_t *buffer_dev, struct gs_keypoint *kps_dev, unsigned *counts_dev,
+                                   unsigned *level_counts_dev, unsigned nkps, unsigned threshold, unsigned n_levels) {
+  if (n == 0) return;
+  GS_ASSERT(img_dev && buffer_dev && kps_dev && counts_dev && w > 0 && h > 0);
+  orb_pyramid_batch(img_dev, w, h, n, buffer_dev, kps_dev, counts_dev, level_counts_dev, nkps, threshold, n_levels, true);
+}
+void gsh_orb_pyramid_batch_times(double ms[5]) {
+  for (int i = 0; i < 5; i++) ms[i] = g_orb_times[i];
+}
+/* every plane of every frame of a batch buffer = that plane of one single-frame buffer: one k_orb_buffer_fill per kMaxZ frames */
+void gsh_orb_pyramid_buffer_fill_batch(uint8_t *buffer_dev, const uint8_t *single_dev, unsigned w, unsigned h,
+                                       unsigned n_levels, unsigned n) {
   unsigned lw[4], lh[4];
   const unsigned L = orb_pyramid_dims(w, h, n_levels, lw, lh);
-  if (level_counts_dev) GS_HIP(hipMemsetAsync(level_counts_dev, 0, (size_t)n * 16, st));
-  if (L == 0 || nkps == 0 || w < 7 || h < 7) { /* the driver's level loop is empty (nanomagick.c:262, :276); gs_fast's loops are (ref :489) */
-    GS_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n * 4, st));
-    return;
+  if (n == 0 || L == 0) return;
+  GS_ASSERT(buffer_dev && single_dev && w > 0 && h > 0);
+  OrbFillPlanes P{};
+  size_t off = 0;
+  unsigned blocks = 0;
+  for (unsigned p = 0; p < 2 * L - 1; p++) { /* levels 1 .. L-1, then score maps 0 .. L-1 */
+    const unsigned l = p < L - 1 ? p + 1 : p - (L - 1);
+    const size_t s = (size_t)lw[l] * lh[l];
+    GS_ASSERT(s < 0x7fffffffull); /* a plane's byte index is 32 bits wide in the kernel's table */
+    const size_t dwords = (s + 2) / 4 + 1; /* 4-byte aligned destination dwords that can touch the plane at any phase */
+    P.off[p] = off, P.size[p] = (unsigned)s, blocks += (unsigned)((dwords + 255) / 256), P.blk_end[p] = blocks;
+    off += s;
   }
-  gsh_pyramid_batch(buffer_dev, img_dev, w, h, n, L);
-  /* plane l of the levels / of the score maps: n frames of lw[l] x lh[l] */
-  const uint8_t *lev[4] = {img_dev, nullptr, nullptr, nullptr};
-  uint8_t *sm[4];
-  size_t fb[4], off = 0;
-  for (unsigned l = 0; l < L; l++) fb[l] = (size_t)lw[l] * lh[l];
-  for (unsigned l = 1; l < L; l++) lev[l] = buffer_dev + off, off += fb[l] * n;
-  for (unsigned l = 0; l < L; l++) sm[l] = buffer_dev + off, off += fb[l] * n;
-  const unsigned per = nkps / L, cap_last = std::min(nkps * 4u, 5000u);
+  P.np = 2 * L - 1;
+  GS_ASSERT(buffer_dev + (size_t)n * off <= single_dev || single_dev + off <= buffer_dev); /* the two buffers must not overlap */
   for_frames(n, [&](unsigned f0, unsigned nn) {
-    unsigned *cand = (unsigned *)ctx().scratch(SL_KPS, (size_t)nn * cap_last * 48 + 16); /* the last level's: the largest */
-    unsigned *cnt = (unsigned *)ctx().scratch(SL_TOT, (size_t)nn * 4 + 16);
-    unsigned *lc = level_counts_dev ? level_counts_dev + 4 * (size_t)f0 : (unsigned *)ctx().scratch(SL_ORB_LEVELS, (size_t)nn * 16);
-    if (!level_counts_dev) GS_HIP(hipMemsetAsync(lc, 0, (size_t)nn * 16, st));
-    unsigned *out = (unsigned *)kps_dev + (size_t)f0 * nkps * 12;
-    for (unsigned l = 0; l < L; l++) {
-      const bool last = l + 1 == L;
-      if (!last && per == 0) continue; /* level_nkps == 0 (nanomagick.c:276): the level's score maps stay as they are */
-      const unsigned quota = last ? nkps : per; /* the last level's: an upper bound, k_orb_select_level has the frame's own */
-      const unsigned cap = std::min(quota * 4u, 5000u);
-      launch_fast(lev[l] + fb[l] * f0, sm[l] + fb[l] * f0, lw[l], lh[l], nn, cand, cnt, cap, threshold);
-      GS_LAUNCH(k_orb_select_level, dim3(nn), dim3(64), 0, st, (const unsigned *)cand, (const unsigned *)cnt, cap, lw[l], lh[l],
-                nkps, per, l, last ? 1u : 0u, out, lc, counts_dev + f0);
-      GS_LAUNCH(k_orb_describe_level, dim3(quota, nn), dim3(256), 0, st, lev[l] + fb[l] * f0, lw[l], lh[l], fb[l], out,
-                (const unsigned *)lc, nkps, l);
-    }
+    GS_LAUNCH(k_orb_buffer_fill, dim3(blocks, nn), dim3(256), 0, ctx().s(), buffer_dev, single_dev, P, n, f0);
   });
 }
 void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct gs_keypoint *k2,

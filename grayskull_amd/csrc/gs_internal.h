@@ -211,6 +211,7 @@ struct Ctx {
    * expander of an earlier chunk is done) */
   hipEvent_t ev_guess[kMaxChunks] = {};
   hipEvent_t ev_switch = nullptr; /* gsh_set_stream: the stream entered waits for what was enqueued on the one left */
+  hipEvent_t ev_pin = nullptr;    /* gsh_orb_extract_pyramid_batch: behind the host-to-device copy out of the pinned trig staging */
   void ensure_side() {
     if (side) return;
     {
@@ -302,6 +303,8 @@ struct Ctx {
     prof_n = 0;
     if (ev_switch) (void)hipEventDestroy(ev_switch);
     ev_switch = nullptr;
+    if (ev_pin) (void)hipEventDestroy(ev_pin);
+    ev_pin = nullptr;
     if (side) {
       (void)hipStreamDestroy(side), (void)hipEventDestroy(ev_join);
       for (auto &e : ev_chunk) (void)hipEventDestroy(e), e = nullptr;

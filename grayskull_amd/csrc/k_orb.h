@@ -470,6 +470,133 @@ __global__ __launch_bounds__(256) void k_orb_describe_level(const uint8_t *img, 
   }
 }
 
+/* ------------------------------------------------------------------ pyramid ORB over a batch, libm flavour */
+/* k_orb_describe_level cut in two at the trig, for the flavour whose atan2f / sinf are glibc's and run on the host
+ * (ref :100-101): the moments of every kept keypoint of every level in ONE launch, the round trip, then every descriptor in
+ * one launch.  The selection (k_orb_select_level) needs no trig, so all levels' records and lc exist before either runs.
+ * The levels of a launch's frames, by value: plane l starts at img[l] (the launch's first frame), frames fb[l] apart. */
+struct OrbLevelTab {
+  const uint8_t *img[4];
+  size_t fb[4];
+  unsigned w[4], h[4];
+};
+/* block k of frame f takes record k of the frame's packed list, k < lc[4f] + .. + lc[4f + 3]; its level is the number of
+ * prefix sums of lc[4f ..] that k has reached (levels that did not run count 0 records) */
+GS_DEV unsigned orb_level_of(const unsigned *lc, unsigned f, unsigned k, unsigned &total) {
+  const unsigned c0 = lc[4u * f], c1 = lc[4u * f + 1], c2 = lc[4u * f + 2], c3 = lc[4u * f + 3]; /* block-uniform, requested together */
+  total = c0 + c1 + c2 + c3;
+  return (k >= c0 ? 1u : 0u) + (k >= c0 + c1 ? 1u : 0u) + (k >= c0 + c1 + c2 ? 1u : 0u);
+}
+/* The integer disc moments of k_orb_describe_level at the record's unscaled coordinates in its level's
+ * plane -> mom[(f * nkps + k) * 2] = (m01, m10).  grid (nkps, frames of the launch), block 256; kps / lc / mom: the launch's
+ * first frame. */
+__global__ __launch_bounds__(256) void k_orb_moments_levels(OrbLevelTab T, const unsigned *kps, const unsigned *lc, unsigned nkps,
+                                                           int *mom) {
+  __shared__ int part[2][4];
+  const unsigned f = blockIdx.y, k = blockIdx.x, i = threadIdx.x;
+  unsigned kept;
+  const unsigned level = orb_level_of(lc, f, k, kept);
+  if (k >= kept) return; /* whole block */
+  const unsigned *kp = kps + ((size_t)f * nkps + k) * 12u;
+  const unsigned x = kp[0], y = kp[1];
+  const int r = 15, side = 2 * r + 1, total = side * side;
+  const PxReader px(T.img[level] + (size_t)f * T.fb[level], T.w[level], T.h[level]);
+  int m01 = 0, m10 = 0;
+  px.with([&](auto SM) {
+    int I[4], dyv[4], dxv[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int t = (int)i + 256 * u;
+      dyv[u] = t / side - r, dxv[u] = t % side - r;
+      const unsigned sx = x + (unsigned)dxv[u], sy = y + (unsigned)dyv[u];
+      I[u] = (int)px.template get<decltype(SM)::value>(sx, sy, t < total && dxv[u] * dxv[u] + dyv[u] * dyv[u] <= r * r);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) m01 += dyv[u] * I[u], m10 += dxv[u] * I[u];
+  });
+  m01 = wave_sum_i(m01), m10 = wave_sum_i(m10);
+  if ((i & 63u) == 0) part[0][i >> 6] = m01, part[1][i >> 6] = m10;
+  __syncthreads();
+  if (i == 0) {
+    int *o = mom + ((size_t)f * nkps + k) * 2u;
+    o[0] = part[0][0] + part[0][1] + part[0][2] + part[0][3], o[1] = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+  }
+}
+/* The rotated BRIEF of k_orb_describe_level (and of k_brief) with the host's trig: trig[(f * nkps + k) * 3] =
+ * {angle, sin, cos} as the host computed them (ref :620, :626).  Stores the angle's bits in dword 3 and the descriptor, then
+ * shifts x and y left by the level -- after every thread has used them.  Same grid and block as k_orb_moments_levels. */
+__global__ __launch_bounds__(256) void k_orb_brief_levels(OrbLevelTab T, unsigned *kps, const unsigned *lc, unsigned nkps,
+                                                         const float *trig) {
+#ifndef GS_EMU
+#pragma clang fp contract(off)
+#endif
+  const unsigned f = blockIdx.y, k = blockIdx.x, i = threadIdx.x;
+  unsigned kept;
+  const unsigned level = orb_level_of(lc, f, k, kept);
+  if (k >= kept) return; /* whole block */
+  unsigned *kp = kps + ((size_t)f * nkps + k) * 12u;
+  const float *tr = trig + ((size_t)f * nkps + k) * 3u;
+  const unsigned x = kp[0], y = kp[1];
+  const float angle = tr[0], sin_a = tr[1], cos_a = tr[2];
+  const int p0 = k_brief_pattern[4 * i], p1 = k_brief_pattern[4 * i + 1];
+  const int p2 = k_brief_pattern[4 * i + 2], p3 = k_brief_pattern[4 * i + 3];
+  const float m00 = (float)p0 * cos_a, m01f = (float)p1 * sin_a;
+  const float m10f = (float)p0 * sin_a, m11 = (float)p1 * cos_a;
+  const float n00 = (float)p2 * cos_a, n01 = (float)p3 * sin_a;
+  const float n10 = (float)p2 * sin_a, n11 = (float)p3 * cos_a;
+  const float dx1 = m00 - m01f, dy1 = m10f + m11, dx2 = n00 - n01, dy2 = n10 + n11;
+  const unsigned x1 = (unsigned)((int)x + (int)dx1), y1 = (unsigned)((int)y + (int)dy1);
+  const unsigned x2 = (unsigned)((int)x + (int)dx2), y2 = (unsigned)((int)y + (int)dy2);
+  const PxReader px(T.img[level] + (size_t)f * T.fb[level], T.w[level], T.h[level]); /* both pixels requested before either is used */
+  unsigned I1 = 0, I2 = 0;
+  px.with([&](auto SM) { I1 = px.template get<decltype(SM)::value>(x1, y1), I2 = px.template get<decltype(SM)::value>(x2, y2); });
+  const uint64_t m = ballot(I1 > I2);
+  if (lane_id() == 0) {
+    const unsigned wv = i >> 6;
+    kp[4 + 2 * wv] = (uint32_t)m, kp[4 + 2 * wv + 1] = (uint32_t)(m >> 32);
+  }
+  __syncthreads(); /* every thread has used the record's x and y */
+  if (i == 0) {
+    kp[3] = __builtin_bit_cast(uint32_t, angle);
+    if (level) kp[0] = x << level, kp[1] = y << level;
+  }
+}
+
+/* gsh_orb_pyramid_buffer_fill_batch: every plane of every frame of a level-major batch buffer = that plane of one
+ * single-frame buffer.  Plane p (size[p] bytes) lies at off[p] of the single buffer and, for frame f of n, at n * off[p] +
+ * f * size[p] of the batch.  A thread takes one dword of the DESTINATION at a 4-byte aligned address (whatever the phase of
+ * the source: its four bytes are byte loads from clamped indices, served by the cache; the single buffer is a few MB) and
+ * the edge dwords of a plane go out byte by byte.  blk_end[p]: the blocks of planes 0 .. p.
+ * grid (blk_end[np - 1], frames of the launch), block 256. */
+struct OrbFillPlanes {
+  size_t off[7];
+  unsigned size[7], blk_end[7];
+  unsigned np;
+};
+__global__ __launch_bounds__(256) void k_orb_buffer_fill(uint8_t *dst, const uint8_t *single, OrbFillPlanes P, unsigned n, unsigned f0) {
+  unsigned p = 0;
+  while (p + 1 < P.np && blockIdx.x >= P.blk_end[p]) p++; /* block-uniform */
+  const unsigned b = blockIdx.x - (p ? P.blk_end[p - 1] : 0u), s = P.size[p];
+  const uint8_t *src = single + P.off[p];
+  uint8_t *d = dst + (size_t)n * P.off[p] + (size_t)(f0 + blockIdx.y) * s;
+  const long long lead = (long long)((uintptr_t)d & 3u);
+  const long long i0 = 4ll * ((long long)b * 256 + threadIdx.x) - lead; /* d + i0 is 4-byte aligned */
+  if (i0 >= (long long)s) return;
+  uint32_t v[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const long long i = i0 + j;
+    v[j] = src[i < 0 ? 0 : i >= (long long)s ? (long long)s - 1 : i];
+  }
+  if (i0 >= 0 && i0 + 4 <= (long long)s) {
+    *(uint32_t *)(d + i0) = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (i0 + j >= 0 && i0 + j < (long long)s) d[i0 + j] = (uint8_t)v[j];
+  }
+}
+
 /* keypoint record = 12 dwords, descriptor at dword 4 (grayskull.h:42-47).
  * One WAVE per query: the 64 lanes stride over the train descriptors, each keeping the
  * reference's (best, second, first-argmin) state; states merge with

@@ -31,7 +31,12 @@
  *                       crosses like nanomagick does and listed in <out>.keypoints.txt ("x y response")
  *   orb <template.pgm>  nanomagick's pyramid ORB matcher (nanomagick.c:245-345): 3-level gs_orb_extract of the
  *                       template and of the frame (2500 keypoints, threshold 20), gs_match_orb (300, 60.0),
- *                       the stitched picture with the 15 best matches drawn, and <out>.orb.txt
+ *                       the stitched picture with the 15 best matches drawn, and <out>.orb.txt.  The template goes
+ *                       through gsh_orb_extract_pyramid_batch once per worker (n = 1; its keypoints stay on the device,
+ *                       the scratch buffer it leaves behind is kept); per slice: gsh_orb_pyramid_buffer_fill_batch
+ *                       (every frame's pyramid is built over that buffer, as in a nanomagick process),
+ *                       gsh_orb_extract_pyramid_batch and gsh_match_orb_batch over the slice, one download.  The sort,
+ *                       the sidecar and the drawing stay per-file host code
  *   faces <n>           gs_integral + gs_lbp_detect (cap 100, scale 1.2, 1..4, step n) on the GPU with
  *                       the cascade blob given by --cascade; boxes drawn like nanomagick, listed in
  *                       <out>.faces.txt ("x y w h").  (nanomagick's 640x480 limit is its static buffer
@@ -587,9 +592,10 @@ static void *worker(void *arg) {
   }
   /* orb <template.pgm>: the template is read once and lives on the device */
   struct frame tmpl;
-  uint8_t *tmpl_host = NULL, *tmpl_dev = NULL;
-  struct gs_keypoint *tkps = NULL, *skps = NULL;
-  struct gs_match *matches = NULL;
+  uint8_t *tmpl_host = NULL, *tmpl_dev = NULL, *tmpl_buf = NULL; /* tmpl_buf (host): the scratch buffer as the template's extraction left it */
+  size_t tmpl_buf_bytes = 0;
+  struct gs_keypoint *tkps = NULL, *tkps_dev = NULL;
+  unsigned *tcnt_dev = NULL, nt = 0;
   memset(&tmpl, 0, sizeof tmpl);
   if (term && term->v == V_ORB) {
     tmpl.path = term->raw;
@@ -598,13 +604,25 @@ static void *worker(void *arg) {
       if (jb->device == 0) printf("Error: Cannot load template image %s\n", tmpl.path); /* nanomagick.c:294, on stdout */
       tmpl.w = 0;
     } else {
+      /* nanomagick.c:303: the template's pyramid in the zeroed scratch buffer; what it leaves there is what every
+       * scene's pyramid is built over (below) */
+      uint8_t *buf_dev;
+      tmpl_buf_bytes = gsh_orb_pyramid_buffer_bytes(tmpl.w, tmpl.h, 3);
       tmpl_dev = (uint8_t *)gsh_malloc((size_t)tmpl.w * tmpl.h);
+      buf_dev = (uint8_t *)gsh_malloc(tmpl_buf_bytes);
+      tkps_dev = (struct gs_keypoint *)gsh_malloc(kOrbKps * sizeof *tkps_dev);
+      tcnt_dev = (unsigned *)gsh_malloc(sizeof *tcnt_dev);
+      tkps = (struct gs_keypoint *)malloc(kOrbKps * sizeof *tkps);
+      tmpl_buf = (uint8_t *)malloc(tmpl_buf_bytes);
+      if (!tkps || !tmpl_buf) gsb_oom(__LINE__);
       gsh_upload(tmpl_dev, tmpl_host, (size_t)tmpl.w * tmpl.h);
+      gsh_memset(buf_dev, 0, tmpl_buf_bytes);
+      gsh_orb_extract_pyramid_batch(tmpl_dev, tmpl.w, tmpl.h, 1, buf_dev, tkps_dev, tcnt_dev, NULL, kOrbKps, 20, 3);
+      gsh_download(&nt, tcnt_dev, sizeof nt);
+      gsh_download(tkps, tkps_dev, (size_t)nt * sizeof *tkps);
+      gsh_download(tmpl_buf, buf_dev, tmpl_buf_bytes);
+      gsh_free(buf_dev);
     }
-    tkps = (struct gs_keypoint *)malloc(5000 * sizeof *tkps); /* nanomagick.c:301 */
-    skps = (struct gs_keypoint *)malloc(5000 * sizeof *skps);
-    matches = (struct gs_match *)malloc(kOrbMatches * sizeof *matches);
-    if (!tkps || !skps || !matches) gsb_oom(__LINE__);
   }
 
   for (g = 0; g < jb->ngroups; g++) {
@@ -618,8 +636,10 @@ static void *worker(void *arg) {
     int *idx;
     double t0;
     /* terminal-verb buffers */
-    uint8_t *orb_buf = NULL;
+    uint8_t *orb_buf = NULL, *orb_batch = NULL; /* orb: one frame's scratch buffer after the template, the slice's buffers */
     size_t orb_buf_bytes = 0;
+    struct gs_match *matches_dev = NULL, *matches_host = NULL;
+    unsigned *mcnt_dev = NULL, *mcnt_host = NULL, orb_calls = 0;
     uint8_t *score = NULL;
     uint64_t *sums_dev = NULL, *sums_host = NULL;
     struct gs_keypoint *kps_dev = NULL, *kps_host = NULL;
@@ -693,11 +713,27 @@ static void *worker(void *arg) {
     sums_host = (uint64_t *)malloc((size_t)cap * 8);
     if (!sums_host) gsb_oom(__LINE__);
     if (term && term->v == V_ORB) {
-      /* one scratch buffer for both pyramids, like nanomagick's (there: a static 1 MiB array, which a
-       * frame beyond ~700x500 overruns; here: as large as the bigger pyramid needs) */
-      const size_t a = tmpl.w ? gsh_orb_pyramid_buffer_bytes(tmpl.w, tmpl.h, 3) : 0, b = gsh_orb_pyramid_buffer_bytes(ow, oh, 3);
-      orb_buf_bytes = a > b ? a : b;
-      orb_buf = (uint8_t *)gsh_malloc(orb_buf_bytes);
+      if (tmpl.w) {
+        /* one scratch buffer for both pyramids, like nanomagick's (there: a static 1 MiB array, which a
+         * frame beyond ~700x500 overruns; here: as large as the bigger pyramid needs).  It starts zeroed in every
+         * nanomagick process and the scene's pyramid is built over what the template's left behind (its never-written
+         * score-map frames are read by the NMS): orb_buf is that state, the start of every frame's buffer of a slice */
+        const size_t b = gsh_orb_pyramid_buffer_bytes(ow, oh, 3);
+        orb_buf_bytes = tmpl_buf_bytes > b ? tmpl_buf_bytes : b;
+        orb_buf = (uint8_t *)gsh_malloc(orb_buf_bytes);
+        gsh_memset(orb_buf, 0, orb_buf_bytes);
+        gsh_upload(orb_buf, tmpl_buf, tmpl_buf_bytes);
+        orb_batch = (uint8_t *)gsh_malloc(gsh_orb_pyramid_batch_buffer_bytes(ow, oh, 3, cap));
+        kps_dev = (struct gs_keypoint *)gsh_malloc((size_t)cap * kOrbKps * sizeof *kps_dev);
+        kps_host = (struct gs_keypoint *)malloc((size_t)cap * kOrbKps * sizeof *kps_host);
+        matches_dev = (struct gs_match *)gsh_malloc((size_t)cap * kOrbMatches * sizeof *matches_dev);
+        matches_host = (struct gs_match *)malloc((size_t)cap * kOrbMatches * sizeof *matches_host);
+        cnt_dev = (unsigned *)gsh_malloc((size_t)cap * sizeof(unsigned));
+        mcnt_dev = (unsigned *)gsh_malloc((size_t)cap * sizeof(unsigned));
+        cnt_host = (unsigned *)malloc((size_t)cap * sizeof(unsigned));
+        mcnt_host = (unsigned *)malloc((size_t)cap * sizeof(unsigned));
+        if (!kps_host || !matches_host || !cnt_host || !mcnt_host) gsb_oom(__LINE__);
+      }
     } else if (term) {
       const size_t ofb = (size_t)ow * oh;
       cnt_dev = (unsigned *)gsh_malloc((size_t)cap * sizeof(unsigned));
@@ -743,6 +779,11 @@ static void *worker(void *arg) {
       } else if (term && term->v == V_FACES) { /* nanomagick.c:362-364 */
         gsh_integral_batch(p.cur, ow, oh, nb, ii);
         gsh_lbp_detect_batch(dc, ii, ow, oh, nb, rects_dev, cnt_dev, kFaceCap, 1.2f, 1.0f, 4.0f, term->a[0]);
+      } else if (term && term->v == V_ORB && tmpl.w) { /* nanomagick.c:304-306 for every frame of the slice */
+        gsh_orb_pyramid_buffer_fill_batch(orb_batch, orb_buf, ow, oh, 3, nb);
+        gsh_orb_extract_pyramid_batch(p.cur, ow, oh, nb, orb_batch, kps_dev, cnt_dev, NULL, kOrbKps, 20, 3);
+        gsh_match_orb_batch(tkps_dev, kOrbKps, tcnt_dev, 1, kps_dev, kOrbKps, cnt_dev, nb, nb, matches_dev, mcnt_dev, kOrbMatches, 60.0f);
+        orb_calls++;
       }
       gsh_checksum_batch(p.cur, (size_t)ow * oh, nb, sums_dev); /* of the final plane, on the device (what bench.py checks) */
       gsh_sync();
@@ -751,7 +792,12 @@ static void *worker(void *arg) {
       t0 = now_ms();
       gsh_download(stage, p.cur, (size_t)ow * oh * nb);
       gsh_download(sums_host, sums_dev, (size_t)nb * 8);
-      if (term && term->v != V_ORB) {
+      if (term && term->v == V_ORB && tmpl.w) {
+        gsh_download(cnt_host, cnt_dev, (size_t)nb * sizeof(unsigned));
+        gsh_download(mcnt_host, mcnt_dev, (size_t)nb * sizeof(unsigned));
+        gsh_download(matches_host, matches_dev, (size_t)nb * kOrbMatches * sizeof *matches_host);
+        gsh_download(kps_host, kps_dev, (size_t)nb * kOrbKps * sizeof *kps_host);
+      } else if (term && term->v != V_ORB) {
         gsh_download(cnt_host, cnt_dev, (size_t)nb * sizeof(unsigned));
         if (term->v == V_KEYPOINTS) gsh_download(kps_host, kps_dev, (size_t)nb * kFastCap * sizeof *kps_host);
         else gsh_download(rects_host, rects_dev, (size_t)nb * kFaceCap * sizeof *rects_host);
@@ -770,8 +816,10 @@ static void *worker(void *arg) {
         }
         jb->file_sum[idx[lo + b0 + f]] = sums_host[f];
         jb->file_cnt[idx[lo + b0 + f]] = (term && term->v != V_ORB) ? cnt_host[f] : 0;
-        if (term && term->v == V_ORB) { /* nanomagick.c:292-345, frame by frame like one process per file */
-          unsigned nt, nsc, nm, k, x, y;
+        if (term && term->v == V_ORB) { /* nanomagick.c:308-345 on the slice's downloaded records, file by file */
+          unsigned nsc, nm, k, x, y;
+          const struct gs_keypoint *skps = kps_host + (size_t)f * kOrbKps;
+          struct gs_match *matches = matches_host + (size_t)f * kOrbMatches;
           FILE *rec;
           uint8_t *out;
           if (!tmpl.w) { /* the verb returned without an image (nanomagick.c:294-297) */
@@ -779,12 +827,7 @@ static void *worker(void *arg) {
             fi->failed = 1, jb->rc = 1;
             continue;
           }
-          /* the scratch buffer starts zeroed in every nanomagick process and the scene's pyramid is built
-           * over what the template's left behind (its never-written score-map frames are read by the NMS) */
-          gsh_memset(orb_buf, 0, orb_buf_bytes);
-          nt = gsh_orb_extract_pyramid(tmpl_dev, tmpl.w, tmpl.h, orb_buf, tkps, kOrbKps, 20, 3);
-          nsc = gsh_orb_extract_pyramid(p.cur + (size_t)ow * oh * f, ow, oh, orb_buf, skps, kOrbKps, 20, 3);
-          nm = gs_match_orb(tkps, nt, skps, nsc, matches, kOrbMatches, 60.0f);
+          nsc = cnt_host[f], nm = mcnt_host[f];
           snprintf(path, sizeof path, "%s/%s.orb.txt", jb->outdir, base_name(fi->path));
           rec = fopen(path, "w");
           if (rec) fprintf(rec, "Template: %u keypoints, Scene: %u keypoints, Matches: %u\n", nt, nsc, nm);
@@ -869,6 +912,8 @@ static void *worker(void *arg) {
     }
     if (jb->verbose)
       fprintf(stderr, "gpu %d group %d: %u of %u frame(s) %ux%u -> %ux%u\n", jb->device, g, n, ngroup, w, h, ow, oh);
+    if (jb->verbose && term && term->v == V_ORB && tmpl.w)
+      fprintf(stderr, "gpu %d group %d: orb: template %u keypoint(s), %u frame(s) in %u batched call(s)\n", jb->device, g, nt, n, orb_calls);
     gsh_free(p.cur);
     gsh_free(p.other);
     if (p.third) gsh_free(p.third);
@@ -882,6 +927,11 @@ static void *worker(void *arg) {
     free(p.cnt_host);
     gsh_host_free(stage);
     gsh_free(orb_buf);
+    gsh_free(orb_batch);
+    gsh_free(matches_dev);
+    gsh_free(mcnt_dev);
+    free(matches_host);
+    free(mcnt_host);
     gsh_free(score);
     gsh_free(kps_dev);
     gsh_free(ii);
@@ -899,10 +949,11 @@ static void *worker(void *arg) {
   if (dc) gsh_cascade_destroy(dc);
   free(mine.raw);
   gsh_free(tmpl_dev);
+  gsh_free(tkps_dev);
+  gsh_free(tcnt_dev);
   free(tmpl_host);
+  free(tmpl_buf);
   free(tkps);
-  free(skps);
-  free(matches);
   { /* SURVEY 8(e) collectives (2) and (4): every worker learns every file's count + checksum (all-gather of the nf-long
      * arrays, zero where a worker owns nothing: a file has one owner, so the column sums are the owners' values), and the
      * job's wall time is the all-reduce(max) of the workers' */

@@ -263,6 +263,36 @@ void gsh_orb_extract_pyramid_batch_nostdlib(const uint8_t *img_dev, unsigned w, 
                                             unsigned *level_counts_dev /* n x 4, may be NULL */,
                                             unsigned nkps, unsigned threshold, unsigned n_levels);
 
+/* The same for the reference's DEFAULT build, whose atan2f / sinf are glibc's (ref :100-101): what `nanomagick orb` computes.
+ * Arguments, buffer layout, output layout, the skipped levels, the degenerate cases, n == 0, the GS_ASSERTs and the frame
+ * split are those of gsh_orb_extract_pyramid_batch_nostdlib; frame f's result is what extract_pyramid_orb_nm of the default
+ * build returns and writes, bit for bit (angles and descriptors differ from the GS_NO_STDLIB flavour's for nearly every
+ * keypoint).  The records and counts stay on the device, in the layout gsh_match_orb_batch reads.
+ * The trig runs on the host, as in gsh_orb_extract_batch: FAST and the selection of every level of every frame, the disc
+ * moments of every kept keypoint in one launch, ONE round trip for the whole call (moments and counts down, {angle, sin,
+ * cos} up; from 4096 kept keypoints the host half runs on the library's thread pool), the descriptors in one launch.  The
+ * call BLOCKS for that round trip -- also under gsh_set_async(1) -- and returns once the upload has left its pinned staging;
+ * what it enqueues behind the round trip is stream-ordered on the current stream like every other batch entry. */
+void gsh_orb_extract_pyramid_batch(const uint8_t *img_dev, unsigned w, unsigned h, unsigned n,
+                                   uint8_t *buffer_dev, struct gs_keypoint *kps_dev, unsigned *counts_dev,
+                                   unsigned *level_counts_dev /* n x 4, may be NULL */,
+                                   unsigned nkps, unsigned threshold, unsigned n_levels);
+
+/* Measurement hook (scripts/ubench_orb_pyramid_libm.py): where this thread's last gsh_orb_extract_pyramid_batch call that ran
+ * under gsh_profile(1) spent its time, in ms: [0] device work before the round trip, [1] the copy down, [2] the host trig,
+ * [3] the copy up, [4] device work after it.  Under gsh_profile(1) the call ends synchronised.  Zeros before such a call. */
+void gsh_orb_pyramid_batch_times(double ms[5]);
+
+/* Every plane p of every frame f of a batch buffer (gsh_orb_pyramid_batch_buffer_bytes(w, h, n_levels, n) bytes, the
+ * level-major layout above) becomes a copy of plane p of single_dev, one frame's buffer in gsh_orb_extract_pyramid's layout
+ * (gsh_orb_pyramid_buffer_bytes(w, h, n_levels) bytes): n identical frames.  For callers that reproduce a process in which
+ * the pyramid is built over what an earlier extraction left behind -- `nanomagick orb` builds the scene's over the
+ * template's -- since the never-written 3-px frames of the score maps are read by the NMS.  ONE launch per kMaxZ frames
+ * (GSH_TUNE_FRAMES_PER_LAUNCH).  Device pointers at any alignment, stream-ordered.  n == 0 or n_levels == 0 writes nothing
+ * and checks nothing.  GS_ASSERT: non-NULL pointers, w and h non-zero, the two buffers do not overlap. */
+void gsh_orb_pyramid_buffer_fill_batch(uint8_t *buffer_dev, const uint8_t *single_dev,
+                                       unsigned w, unsigned h, unsigned n_levels, unsigned n);
+
 /* All pointers device; matches: max_matches records, the first *count written, the rest not; count: 1 u32.
  * Stream-ordered. */
 void gsh_match_orb_dev(const struct gs_keypoint *k1, unsigned n1, const struct gs_keypoint *k2,
