@@ -253,3 +253,17 @@ def blurred_noise(rng, h, w, passes=2):
     for _ in range(passes):
         a = (a + np.roll(a, 1, 0) + np.roll(a, -1, 0) + np.roll(a, 1, 1) + np.roll(a, -1, 1)) / 5
     return np.clip(a, 0, 255).astype(np.uint8)
+
+
+def emu_frames():
+    """small frames that still span several 64-px words and many rows; widths off the word size"""
+    rng = np.random.default_rng(2024)
+    out = []
+    for (h, w) in ((23, 70), (40, 131), (17, 200), (64, 64), (9, 257)):
+        for d in (0.5, 0.59, 0.65, 0.8):
+            out.append(("random %dx%d d=%.2f" % (w, h, d), random_mask(rng, h, w, d)))
+    out.append(("checkerboard", checkerboard(21, 133)))
+    out.append(("spiral", spiral(41, 150)))
+    out.append(("maze", maze(rng, 37, 139)))
+    out.append(("dots", dots(48, 130, period=6, size=3)))
+    return out

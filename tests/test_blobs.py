@@ -174,18 +174,7 @@ def _ref():
     return bc.Ref()
 
 
-def emu_frames():
-    """small frames that still span several 64-px words and many rows; widths off the word size"""
-    rng = np.random.default_rng(2024)
-    out = []
-    for (h, w) in ((23, 70), (40, 131), (17, 200), (64, 64), (9, 257)):
-        for d in (0.5, 0.59, 0.65, 0.8):
-            out.append(("random %dx%d d=%.2f" % (w, h, d), bc.random_mask(rng, h, w, d)))
-    out.append(("checkerboard", bc.checkerboard(21, 133)))
-    out.append(("spiral", bc.spiral(41, 150)))
-    out.append(("maze", bc.maze(rng, 37, 139)))
-    out.append(("dots", bc.dots(48, 130, period=6, size=3)))
-    return out
+emu_frames = bc.emu_frames  # the generator lives in blob_cases.py: tests/cap_sweep_cases.py sweeps the same frames
 
 
 def test_blobs_match_reference_emulated(emu):
