@@ -171,6 +171,11 @@ _SIGS = {
                                          C.c_void_p]),
     "gsh_locate_templates_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsh_locate_template_windows_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                                  C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
+    "gsh_match_template_windows_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                                 C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]),
+    "gsh_search_windows_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]),
     "gsh_blobs_batch": (None, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_uint]),
     "gsh_blob_corners_batch": (None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
@@ -701,6 +706,43 @@ class Grayskull:
         n, ih, iw = img.shape
         m, th, tw = tmpl.shape
         self.c.gsh_locate_templates_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, m, _ptr(best), _ptr(score), _ptr(winner))
+
+    @staticmethod
+    def _windows(windows, tmpl):
+        """(nwin, tw, th, ntmpl): windows (nwin, 4) int32 / uint32 {x, y, w, h} or (nwin) RECT_DTYPE; tmpl (th, tw) -- one
+        for all windows -- or (nwin, th, tw)"""
+        nwin = int(windows.shape[0])
+        if not (windows.ndim == 1 or (windows.ndim == 2 and int(windows.shape[1]) == 4)):
+            raise ValueError("expected windows (nwin, 4) {x, y, w, h} or (nwin) RECT_DTYPE")
+        tw, th, ntmpl = Grayskull._templates(tmpl, nwin)
+        return nwin, tw, th, ntmpl
+
+    def locate_template_windows_batch(self, img, tmpl, windows, max_size, best, score=None, frame_of=None):
+        """gsh_locate_template_windows_batch: per window p = windows[p] (x, y, w, h in frame coordinates) of frame frame_of[p]
+        (frame p when frame_of is None) of img (n, ih, iw) uint8, gs_find_best_match(gs_match_template(gs_crop(...), tmpl)):
+        best (nwin, 2) uint32 / int32 {x, y} in FRAME coordinates, score (nwin) uint8 or None.  max_size = (max_ww, max_wh):
+        the host's upper bound on a window's size.  An invalid window gets {0xFFFFFFFF, 0xFFFFFFFF} and score 0.  windows,
+        frame_of, best and score live where img lives and are read and written there"""
+        n, ih, iw = self._nhw(img)
+        nwin, tw, th, ntmpl = self._windows(windows, tmpl)
+        self.c.gsh_locate_template_windows_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, ntmpl, _ptr(windows), _ptr(frame_of), nwin,
+                                                 int(max_size[0]), int(max_size[1]), _ptr(best), _ptr(score))
+
+    def match_template_windows_batch(self, result, img, tmpl, windows, max_size, frame_of=None):
+        """gsh_match_template_windows_batch: result (nwin, max_wh - th + 1, max_ww - tw + 1) uint8 holds one SLOT per window;
+        window p's map of (h - th + 1) rows of (w - tw + 1) bytes lies at the slot's start with row pitch w - tw + 1, the
+        rest of the slot -- and the whole slot of an invalid window -- is left untouched"""
+        n, ih, iw = self._nhw(img)
+        nwin, tw, th, ntmpl = self._windows(windows, tmpl)
+        self.c.gsh_match_template_windows_batch(_ptr(img), iw, ih, n, _ptr(tmpl), tw, th, ntmpl, _ptr(windows), _ptr(frame_of), nwin,
+                                                int(max_size[0]), int(max_size[1]), _ptr(result))
+
+    def search_windows_batch(self, at, box, margin, frame_size, windows):
+        """gsh_search_windows_batch: windows (nwin, 4) = the box (at[p].x, at[p].y, box = (bw, bh)) grown by margin = (mx, my) on
+        every side and clipped to the frame, frame_size = (iw, ih); at (nwin, 2) {x, y}, e.g. locate's best.  A point outside
+        the frame -- locate's invalid sentinel -- gives (0, 0, 0, 0), an invalid window"""
+        self.c.gsh_search_windows_batch(_ptr(at), int(at.shape[0]), int(box[0]), int(box[1]), int(margin[0]), int(margin[1]),
+                                        int(frame_size[0]), int(frame_size[1]), _ptr(windows))
 
     def blobs_batch(self, img, labels, blobs, counts, nblobs):
         """gsh_blobs_batch: img (n, h, w) uint8, labels (n, h, w) uint16 [or int16], blobs (n, nblobs, 8) int32 (one

@@ -14,6 +14,7 @@
 #include "k_resize.h"
 #include "k_stencil.h"
 #include "k_tmatch.h"
+#include "k_tmatch_win.h"
 
 namespace gsi {
 
@@ -722,6 +723,54 @@ static void tm_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, c
   if (!result) GS_LAUNCH(k_best_from_keys, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, rw, (unsigned *)best, score);
 }
 
+/* ---- templates inside windows read on the device (k_tmatch_win.h; docs/design/stencils.md 3.6) ---------------------------- */
+/* The bands of k_tmatch_windows: at most kTmwBandCols template columns at a time, and as many template rows as keep
+ * (31 + rows) image rows and the rows of the template within kTmwLdsPlan.  ipdw: the dwords a lane can touch (8 + the band's
+ * dwords), rounded up to 8 mod 16 (the bank rule of k_tmatch_win.h).  The widest band: 72 + 64 dwords a row, 28 rows. */
+struct TmWinForm {
+  unsigned band_rows, band_cols, ipdw, tpdw;
+  size_t lds;
+};
+static TmWinForm tm_win_form(unsigned tw, unsigned th) {
+  TmWinForm f;
+  f.band_cols = std::min(tw, kTmwBandCols);
+  f.tpdw = (f.band_cols + 3) / 4;
+  f.ipdw = f.tpdw + 8;
+  f.ipdw += (8 - f.ipdw % 16 + 16) % 16;
+  const unsigned plan = kTmwLdsPlan / 4;
+  f.band_rows = std::min(th, (plan - (kTmwTile - 1) * f.ipdw) / (f.ipdw + f.tpdw));
+  f.lds = ((size_t)(kTmwTile - 1 + f.band_rows) * f.ipdw + (size_t)f.band_rows * f.tpdw) * 4;
+  return f;
+}
+/* gsh_match_template_windows_batch (result != nullptr) and gsh_locate_template_windows_batch (best != nullptr) */
+static void tm_windows(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
+                       const struct gs_rect *windows_dev, const unsigned *frame_of_dev, unsigned nwin, unsigned max_ww, unsigned max_wh,
+                       uint8_t *result, struct gs_point *best, uint8_t *score) {
+  GS_ASSERT(img && tmpl && windows_dev);
+  GS_ASSERT(iw > 0 && ih > 0 && n > 0 && tw > 0 && th > 0);
+  GS_ASSERT(tw <= max_ww && th <= max_wh);
+  GS_ASSERT(max_ww <= iw && max_wh <= ih);
+  GS_ASSERT(ntmpl == 1 || ntmpl == nwin);
+  GS_ASSERT(frame_of_dev != NULL || nwin <= n);
+  const unsigned mrw = max_ww - tw + 1, mrh = max_wh - th + 1;
+  const TmWinForm f = tm_win_form(tw, th);
+  hipStream_t st = ctx().s();
+  unsigned long long *keys = nullptr;
+  if (!result) {
+    keys = (unsigned long long *)ctx().scratch(SL_BEST, (size_t)nwin * 8);
+    GS_HIP(hipMemsetAsync(keys, 0, (size_t)nwin * 8, st));
+  }
+  TmWinArgs a{img, iw, ih, n, tmpl, tw, th, ntmpl > 1 ? (size_t)tw * th : (size_t)0, (const unsigned *)windows_dev, frame_of_dev, 0u, max_ww, max_wh,
+              result, (size_t)mrw * mrh, keys, f.band_rows, f.band_cols, f.ipdw, f.tpdw};
+  for_frames(nwin, [&](unsigned p0, unsigned nn) {
+    a.z0 = p0;
+    GS_LAUNCH(k_tmatch_windows, dim3((mrw + kTmwTile - 1) / kTmwTile, (mrh + kTmwTile - 1) / kTmwTile, nn), dim3(64, 4), f.lds, st, a);
+  });
+  if (!result)
+    GS_LAUNCH(k_tmw_best, dim3((nwin + 255) / 256), dim3(256), 0, st, (const unsigned long long *)keys, (const unsigned *)windows_dev, frame_of_dev,
+              nwin, tw, th, max_ww, max_wh, iw, ih, n, (unsigned *)best, score);
+}
+
 /* ---- a bank of m templates of one size against every frame (k_tmatch.h: k_match_bank_mfma) ------------------------------------ */
 struct TmBankForm {
   bool valid;
@@ -1262,6 +1311,27 @@ void gsh_locate_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, un
   if (n == 0 || m == 0) return;
   GS_ASSERT(best != NULL);
   tm_bank(img, iw, ih, n, tmpl, tw, th, m, nullptr, best, score, winner);
+}
+void gsh_match_template_windows_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th,
+                                      unsigned ntmpl, const struct gs_rect *windows_dev, const unsigned *frame_of_dev, unsigned nwin,
+                                      unsigned max_ww, unsigned max_wh, uint8_t *result) {
+  if (nwin == 0) return;
+  GS_ASSERT(result != NULL);
+  tm_windows(img, iw, ih, n, tmpl, tw, th, ntmpl, windows_dev, frame_of_dev, nwin, max_ww, max_wh, result, nullptr, nullptr);
+}
+void gsh_locate_template_windows_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n, const uint8_t *tmpl, unsigned tw, unsigned th,
+                                       unsigned ntmpl, const struct gs_rect *windows_dev, const unsigned *frame_of_dev, unsigned nwin,
+                                       unsigned max_ww, unsigned max_wh, struct gs_point *best, uint8_t *score) {
+  if (nwin == 0) return;
+  GS_ASSERT(best != NULL);
+  tm_windows(img, iw, ih, n, tmpl, tw, th, ntmpl, windows_dev, frame_of_dev, nwin, max_ww, max_wh, nullptr, best, score);
+}
+void gsh_search_windows_batch(const struct gs_point *at_dev, unsigned nwin, unsigned bw, unsigned bh, unsigned mx, unsigned my, unsigned iw,
+                              unsigned ih, struct gs_rect *windows_dev) {
+  if (nwin == 0) return;
+  GS_ASSERT(at_dev && windows_dev && bw > 0 && bh > 0 && iw > 0 && ih > 0);
+  GS_LAUNCH(k_search_windows, dim3((nwin + 255) / 256), dim3(256), 0, ctx().s(), (const unsigned *)at_dev, nwin, bw, bh, mx, my, iw, ih,
+            (unsigned *)windows_dev);
 }
 
 

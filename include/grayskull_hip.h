@@ -383,6 +383,43 @@ void gsh_match_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, uns
 void gsh_locate_templates_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
                                 const uint8_t *tmpl, unsigned tw, unsigned th, unsigned m,
                                 struct gs_point *best, uint8_t *score, unsigned *winner);
+/* WINDOWS read on the device: look for a patch only near where it was (a tracker's step).  Per window the result is the
+ * reference's gs_find_best_match(gs_match_template(gs_crop(frame, window), tmpl)), bit for bit.
+ * Common to the three entries: all pointers device pointers; stream-ordered on the current stream, obeying gsh_set_async;
+ * no host synchronisation, no read-back and no table built on the host (the grow-only context scratch may synchronise
+ * when it grows).  nwin == 0 returns before any check or launch.  GS_ASSERT: non-NULL pointers (score may be NULL),
+ * non-zero sizes, tw <= max_ww && th <= max_wh, max_ww <= iw && max_wh <= ih, ntmpl == 1 || ntmpl == nwin, and
+ * nwin <= n when frame_of_dev is NULL.
+ * A window is VALID when its frame index is < n, w >= tw, h >= th, w <= max_ww, h <= max_wh and it lies inside the frame
+ * (x + w <= iw is tested without 32-bit overflow, as gsh_crop_resize_batch does).  Nothing can assert on the device: an
+ * invalid window gets best[p] = {0xFFFFFFFF, 0xFFFFFFFF} and score[p] = 0, and its map bytes are left untouched.
+ * locate: for a valid window with c = gs_crop(frame, window), m = gs_match_template(c, tmpl), b = gs_find_best_match(m):
+ *   best[p] = {window.x + b.x, window.y + b.y} in FRAME coordinates, score[p] = m[b]; the first maximum in the window's
+ *   own raster order wins; an all-zero map gives the window's origin and score 0 (the reference's {0,0}; not the
+ *   invalid sentinel).
+ * match: map p is rw_p x rh_p = (w - tw + 1) x (h - th + 1) bytes with row pitch rw_p, at
+ *   result + p * (max_ww - tw + 1) * (max_wh - th + 1); each map byte is the reference's; the bytes of the slot beyond the
+ *   map are left untouched.
+ * Any template size that fits a window is taken; the frames are neither copied nor required to have iw % 4 == 0. */
+/* nwin windows; window p is windows_dev[p] (frame coordinates) in frame frame_of_dev[p]
+   (frame p when frame_of_dev is NULL; then nwin <= n).  ntmpl == 1: one template for all windows,
+   ntmpl == nwin: template p at tmpl + p*tw*th.  max_ww x max_wh: the host's upper bound on a window's size
+   (it sizes the grid and the map pitch).  Everything else is read on the device. */
+void gsh_locate_template_windows_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
+                                       const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
+                                       const struct gs_rect *windows_dev, const unsigned *frame_of_dev, unsigned nwin,
+                                       unsigned max_ww, unsigned max_wh, struct gs_point *best, uint8_t *score /* may be NULL */);
+void gsh_match_template_windows_batch(const uint8_t *img, unsigned iw, unsigned ih, unsigned n,
+                                      const uint8_t *tmpl, unsigned tw, unsigned th, unsigned ntmpl,
+                                      const struct gs_rect *windows_dev, const unsigned *frame_of_dev, unsigned nwin,
+                                      unsigned max_ww, unsigned max_wh, uint8_t *result);
+/* the glue that makes one time step's `best` the next step's windows with nothing in between:
+ * windows_dev[p] = the box {at.x, at.y, bw, bh} grown by mx / my on every side and clipped to the frame --
+ * x0 = at.x > mx ? at.x - mx : 0, x1 = min(at.x + bw + mx, iw) computed in 64 bits, the same for y, {x0, y0, x1 - x0, y1 - y0}.
+ * A point with x >= iw or y >= ih gives {0, 0, 0, 0} -- the invalid sentinel among them, so invalidity propagates down
+ * a chain.  GS_ASSERT: non-NULL pointers, bw, bh, iw, ih > 0. */
+void gsh_search_windows_batch(const struct gs_point *at_dev, unsigned nwin, unsigned bw, unsigned bh,
+                              unsigned mx, unsigned my, unsigned iw, unsigned ih, struct gs_rect *windows_dev);
 
 /* ---- connected components, blob corners, perspective correction (ref :330, :404, :423) ----------
  * The reference's document-scanner chain (blur -> Otsu threshold -> gs_blobs -> largest blob ->
