@@ -1,13 +1,15 @@
 """Kernel LOGIC parity on CPU: the same kernel sources (grayskull_amd/csrc/k_*.h + gs_*.cpp)
 compiled for the host-fiber SIMT emulator (tests/emu) and compared with the oracle on tiny
 inputs.  This is a development/CI aid for a container without a GPU -- the real parity tests are
-the `-m gpu` ones in test_gpu_parity.py, which run the HIP build on the MI355X."""
+the `-m gpu` ones, which run the HIP build on the MI355X: test_gpu_parity.py, and test_gpu_kernel_logic.py
+for the cases whose bodies live in kernel_logic_cases.py and run here and there."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import kernel_logic_cases as kl
 import parity_cases as pc
 from oracle.pyoracle import Oracle
 from util import assert_same, lena, random_cascade
@@ -61,29 +63,13 @@ def test_next_rows(emu, oracle, shape):
 @pytest.mark.parametrize("shape", [(67, 45), (96, 80), (7, 7), (6, 30), (40, 8), (300, 12), (260, 17), (8, 8), (516, 9),
                                    (64, 40), (48, 7), (32, 16), (1040, 9), (2064, 8)])
 def test_fast(emu, oracle, shape):
-    w, h = shape
-    for strip in (0, 2):  # gsh_tune key 7: 0 LDS tile, 4 px per thread + candidate queue (default), 2 one global byte load per ring pixel
-        emu.tune(7, strip)
-        try:
-            pc.fast(emu, oracle, Oracle.synth(w, h, 5), MEM)
-            rs = np.random.RandomState(1)
-            pc.fast(emu, oracle, rs.randint(0, 256, (h, w)).astype(np.uint8), MEM, threshold=5, caps=(5000, 1))
-            pc.fast(emu, oracle, rs.randint(0, 40, (h, w)).astype(np.uint8), MEM, threshold=30)  # p < t everywhere
-            img = rs.randint(0, 256, (h, w)).astype(np.uint8)
-            for t in (0, 1, 255, 256, 300, 0x7fffffff, 0x80000000, 0xffffff00, 0xffffff01, 0xfffffff0, 0xffffffff):
-                pc.fast(emu, oracle, img, MEM, threshold=t, caps=(5000,))  # incl. thresholds where p + t wraps
-        finally:
-            emu.tune(7, 0)
+    kl.fast_shape(emu, oracle, MEM, shape)
 
 
 def test_fast_score_tiles_that_stick_out_of_the_frame(emu, oracle):
     """k_fast_score_q4<48>: a thread filters 4 pixels of three tile rows, the candidate queue and the in-place path for dense
     tiles span the 48-row tile; frame heights that leave ragged last tiles"""
-    rs = np.random.RandomState(31)
-    for (w, h) in ((70, 23), (131, 77), (64, 38), (200, 135)):
-        pc.fast(emu, oracle, Oracle.synth(w, h, 5), MEM)
-        pc.fast(emu, oracle, rs.randint(0, 256, (h, w)).astype(np.uint8), MEM, threshold=5, caps=(5000,))   # dense: scored in place
-        pc.fast(emu, oracle, (rs.randint(0, 256, (h, w)) * (rs.rand(h, w) < 0.2)).astype(np.uint8), MEM, threshold=40)
+    kl.fast_tiles_that_stick_out(emu, oracle, MEM)
 
 
 def test_fast_tile_kernel_equals_per_pixel_kernel(emu, oracle):
@@ -194,13 +180,7 @@ def test_match_template_on_the_matrix_cores(emu, oracle, case):
 
 def test_template_wider_than_the_lds_tile(emu, oracle):
     """templates wider than 16381 px take the per-tap kernel; 16380 is the widest dot4 / LDS-row case"""
-    rs = np.random.RandomState(2)
-    for (iw, ih, tw, th) in ((16420, 3, 16400, 2), (16400, 2, 16380, 2)):
-        img = rs.randint(0, 256, (ih, iw)).astype(np.uint8)
-        t = rs.randint(0, 256, (th, tw)).astype(np.uint8)
-        r = np.zeros((ih - th + 1, iw - tw + 1), np.uint8)
-        emu.match_template(img, t, r)
-        assert_same(r, oracle.match_template(img, t), "gs_match_template %dx%d" % (tw, th))
+    kl.template_wider_than_the_lds_tile(emu, oracle, (MEM,))
 
 
 def test_orb_batch(emu, oracle):
@@ -283,12 +263,7 @@ def test_lena_pipeline(emu, oracle, kat):
 @pytest.mark.parametrize("radius", [1, 2, 3, 5])
 def test_blur_sobel_batch(emu, oracle, radius):
     """gsh_blur_sobel_batch == gs_blur then gs_sobel into a zeroed image (fused for radius 1..3)"""
-    n, h, w = 2, 21, 64
-    src = np.stack([Oracle.synth(w, h, 40 + i) for i in range(n)])
-    dst = np.full_like(src, 9)
-    emu.blur_sobel_batch(dst, src, radius)
-    for i in range(n):
-        assert np.array_equal(dst[i], oracle.sobel(oracle.blur(src[i], radius))), (radius, i)
+    kl.blur_sobel_batch(emu, oracle, MEM, radius)
 
 
 def test_batch_entry_points(emu, oracle):
@@ -318,44 +293,18 @@ def test_batch_entry_points(emu, oracle):
         assert sums[i] == np.sum(idx * (gen[i].reshape(-1).astype(np.uint64) + 1), dtype=np.uint64)
 
 
-# geom: block shape 64 x 4, 256 x 1, 128 x 2 (gsh_tune key 1 = 1, 3, 2); frame: one of three frame shapes
-STRIP_GEOM_KEY = (1, 3, 2)
-STRIP_FRAMES = {1: (2064, 11), 2: (64, 23), 3: (4112, 4)}
-
-
 @pytest.mark.parametrize("geom", [0, 1, 2])
 @pytest.mark.parametrize("frame", [1, 2, 3])
 def test_strip_launch_tuning_never_changes_results(emu, oracle, geom, frame):
     """gsh_tune: block shape x rows-per-band, incl. bands of 1 row"""
-    w, h = STRIP_FRAMES[frame]
-    try:
-        for T in (0, 1, 5):
-            emu.tune(0, T), emu.tune(1, STRIP_GEOM_KEY[geom])
-            pc.stencils(emu, oracle, Oracle.synth(w, h, w + h + T), MEM, radii=(1, 2, 3))
-    finally:
-        emu.tune(0, 0), emu.tune(1, 0)
+    kl.strip_launch_tuning(emu, oracle, (MEM,), geom, frame)
 
 
 @pytest.mark.parametrize("radius", [1, 2, 3])
 @pytest.mark.parametrize("shape", [(64, 23), (2064, 9), (4112, 5), (32, 3), (48, 4)])
 def test_fused_edge_pipeline_equals_separate_calls(emu, oracle, radius, shape):
     """gsh_edge_pipeline_batch(tmp=NULL): fused blur->sobel->histogram kernel vs the oracle chain"""
-    w, h = shape
-    n = 2
-    src = np.stack([Oracle.synth(w, h, 300 + w + i) for i in range(n)])
-    for T in (0, 1, 3):
-        emu.tune(0, T)
-        out = np.full_like(src, 7)
-        hist = np.zeros((n, 256), np.uint32)
-        thr = np.zeros(n, np.uint8)
-        emu.edge_pipeline_batch(out, None, src, radius, hist, thr)
-        for i in range(n):
-            s = oracle.sobel(oracle.blur(src[i], radius))
-            t = oracle.otsu_threshold(s)
-            assert np.array_equal(hist[i], oracle.histogram(s)), "histogram of the sobel image"
-            assert thr[i] == t
-            assert np.array_equal(out[i], oracle.threshold(s, t))
-    emu.tune(0, 0)
+    kl.fused_edge_pipeline(emu, oracle, MEM, radius, shape)
 
 
 @pytest.mark.parametrize("chunk,n", [(3, 7), (2, 6), (4, 5), (1, 3), (8, 5)])
@@ -554,13 +503,13 @@ def test_pyramid_with_zero_levels_or_zero_keypoints_returns_nothing(emu):
 @pytest.mark.parametrize("r", [15, 36, 37, 60, 90])
 def test_orientation_any_radius_matches_the_reference_float_order(emu, reference, r):
     """beyond r = 36 the moment sums pass 2^24 and the reference's float32 accumulation order matters"""
-    side = 2 * r + 31
-    for seed, img in ((1, Oracle.synth(side, side, r)), (2, np.full((side, side), 251, np.uint8))):
-        img = img.copy()
-        img[: side // 2] //= 3  # a strong vertical gradient: large |m01|
-        got = emu.compute_orientation(img, side // 2, side // 2, r)
-        exp = reference.orientation(img, side // 2, side // 2, r)
-        assert np.float32(got).tobytes() == np.float32(exp).tobytes(), (r, seed, got, exp)
+    kl.orientation(emu, reference, (MEM,), r)
+
+
+@pytest.mark.parametrize("r", [37, 60])
+def test_orientation_nostdlib_beyond_the_exact_radius(emu, r):
+    """the same moments through the GS_NO_STDLIB atan2 polynomial"""
+    kl.orientation_nostdlib(emu, (MEM,), r)
 
 
 def fast_many_frames(g, oracle, n):
@@ -601,22 +550,7 @@ def test_fast_batch_split_over_several_launches(emu, oracle):
 def test_fast_batch_tiles_of_several_frames_in_xcd_order(emu, oracle, order):
     """k_fast_score_q4 numbers its 64 x 16 tiles over the whole batch and hands XCD k the k-th eighth of them (gsh_tune
     key 18 = 1: launch order): 5 frames of 4 x 3 tiles = 60 tiles, so the 1-D grid has four blocks without a tile"""
-    n, h, w = 5, 40, 200
-    frames = np.stack([Oracle.synth(w, h, 30 + f) for f in range(n)])
-    frames[3, 5:30, 20:150] = np.random.RandomState(3).randint(0, 256, (25, 130))
-    sm = np.zeros_like(frames)
-    kps = np.zeros((n, 300, 12), np.uint32)
-    counts = np.zeros(n, np.uint32)
-    try:
-        emu.tune(18, order)
-        emu.fast_batch(frames, sm, kps, counts, 300, 20)
-    finally:
-        emu.tune(18, 0)
-    for f in range(n):
-        ko, smo = oracle.fast(frames[f], 300, 20)
-        assert counts[f] == len(ko), f
-        assert_same(kps[f, :len(ko)].reshape(-1).view(ko.dtype), ko, "frame %d" % f)
-        assert_same(sm[f], smo, "scoremap %d" % f)
+    kl.fast_batch_in_xcd_order(emu, oracle, MEM, order)
 
 
 def test_device_resident_orb_with_the_reference_nostdlib_trig(emu, reference):
@@ -644,51 +578,21 @@ def test_device_resident_orb_with_the_reference_nostdlib_trig(emu, reference):
 def test_fast_with_a_score_map_of_another_size(emu, reference):
     """the reference writes the score map through gs_set and reads it through gs_get (ref :512, :518-524): a map
     smaller or larger than the image is legal, positions outside it read 0 and are never written"""
-    img = Oracle.synth(96, 72, 31)
-    rs = np.random.RandomState(5)
-    for (sw, sh) in ((96, 72), (91, 70), (50, 72), (96, 30), (101, 80), (40, 33), (4, 4)):
-        sm0 = rs.randint(0, 3, (sh, sw)).astype(np.uint8)  # a caller's map is not necessarily zeroed
-        sm = sm0.copy()
-        got = emu.fast(img, sm, 500, 20)
-        exp, sm_exp = reference.fast(img, 500, 20, scoremap=sm0)
-        assert_same(got, exp, "keypoints with a %dx%d map" % (sw, sh))
-        assert_same(sm, sm_exp, "score map %dx%d after the call" % (sw, sh))
+    kl.fast_score_map_of_another_size(emu, reference, (MEM,))
 
 
 def test_histogram_ragged_frames_every_alignment(emu, oracle):
     """k_hist_partial counts whole 16-byte chunks from a queue of loads in flight and the bytes before the
     first / after the last whole chunk one by one: frames of 1 .. 70 bytes and 4 KB +- a few at every base
     alignment (frame f of a batch starts at f * w * h bytes)"""
-    rng = np.random.RandomState(11)
-    for w, h in [(1, 1), (3, 1), (5, 3), (1, 16), (17, 1), (31, 1), (11, 3), (1, 33), (7, 9), (70, 1), (4099, 1), (37, 111),
-                 (256 * 16 * 3 + 5, 1)]:
-        n = 17 if w * h < 5000 else 3
-        a = rng.randint(0, 256, (n, h, w)).astype(np.uint8)
-        hist = np.zeros((n, 256), np.uint32)
-        emu.histogram_batch(a, hist)
-        for f in range(n):
-            assert np.array_equal(hist[f], oracle.histogram(a[f])), (w, h, f)
+    kl.histogram_every_alignment(emu, oracle, MEM)
 
 
 def test_histogram_of_an_image_larger_than_one_launch_frame(emu, oracle):
     """images above 1 GB are counted in pieces (k_hist_partial addresses a frame with 32-bit offsets); gsh_tune key 12
     lowers the piece size so that 1000 .. 70000-byte images take that path: whole pieces + a remainder, odd piece sizes
     (every piece starts at another alignment), batches"""
-    rng = np.random.RandomState(5)
-    try:
-        for piece, (n, h, w) in [(4096, (1, 37, 300)), (1000, (2, 70, 1000)), (333, (3, 9, 111)), (999, (1, 1, 999)), (999, (1, 2, 999)),
-                                 (5000, (1, 1, 4999))]:
-            emu.tune(12, piece)
-            a = rng.randint(0, 256, (n, h, w)).astype(np.uint8)
-            hist = np.zeros((n, 256), np.uint32)
-            emu.histogram_batch(a, hist)
-            for f in range(n):
-                assert np.array_equal(hist[f], oracle.histogram(a[f])), (piece, n, h, w, f)
-            thr = np.zeros(n, np.uint8)
-            emu.otsu_batch(a, hist, thr)
-            assert [int(t) for t in thr] == [oracle.otsu_threshold(a[f]) for f in range(n)]
-    finally:
-        emu.tune(12, 0)
+    kl.histogram_in_pieces(emu, oracle, MEM)
 
 
 @pytest.mark.parametrize("mode", [1, 2])
@@ -709,17 +613,8 @@ def test_box_radii_around_the_quotient_switch_and_up_to_127(emu, oracle):
     """k_box16: the quotient of unclipped rows is one multiply up to r = 31 and the float estimate + fix-up beyond; the
     sliding route serves radii up to 127 (u16 column sums, 128-entry LDS halo).  gs_blur and gs_adaptive_threshold on
     images with a bright half (large sums)"""
-    rng = np.random.RandomState(3)
-    for (w, h) in ((96, 80), (272, 90)):
-        img = rng.randint(0, 256, (h, w)).astype(np.uint8)
-        img[:, :w // 2] |= 0xF0
-        for r in (30, 31, 32, 33, 56, 57, 100, 127):
-            d = np.zeros_like(img)
-            emu.blur(d, img.copy(), r)
-            assert_same(d, oracle.blur(img, r), "gs_blur r=%d %dx%d" % (r, w, h))
-            d = np.zeros_like(img)
-            emu.adaptive_threshold(d, img.copy(), r, -3)
-            assert_same(d, oracle.adaptive_threshold(img, r, -3), "gs_adaptive_threshold r=%d %dx%d" % (r, w, h))
+    for r in kl.ANY_RADII:
+        kl.box_any_radius(emu, oracle, (MEM,), r)
 
 
 @pytest.mark.parametrize("shape", [(32, 17), (48, 40), (272, 33), (96, 17), (1040, 19), (64, 70),
@@ -730,59 +625,13 @@ def test_box_register_ring_kernel_every_radius(emu, oracle, shape):
     threads up to 65, heights down to 2 r + 1, bright images (largest sums), bands of 1 .. h rows, and compare constants
     on both sides of every clamp of the product form.  Ragged widths (w % 16 = 1, 15, 14, ...; round 5): the ring kernel
     over the whole strips with the last one a feeder + k_box_edge (one wave per band) for the last 16 + w % 16 columns."""
-    w, h = shape
-    rng = np.random.RandomState(w + h)
-    imgs = [rng.randint(0, 256, (h, w)).astype(np.uint8), np.full((h, w), 255, np.uint8), Oracle.synth(w, h, 7)]
-    imgs[2][:, : w // 2] |= 0xF0
-    try:
-        for r in range(1, 17):
-            if h < 2 * r + 1:
-                continue  # such frames take k_box16 (covered by the any-radius tests)
-            for k, img in enumerate(imgs):
-                for T in ((0,) if k else (0, 1, 5, 2 * r + 1, 2 * r + 2)):
-                    emu.tune(0, T)
-                    d = np.zeros_like(img)
-                    emu.blur(d, img.copy(), r)  # r <= 3 on these widths is k_blur16; the adaptive form below is the ring kernel
-                    assert_same(d, oracle.blur(img, r), "gs_blur r=%d T=%d img %d" % (r, T, k))
-                    for c in ((5, -7, 300, -300, 255, -255, 256, 0) if T == 0 else (5,)):
-                        d = np.zeros_like(img)
-                        emu.adaptive_threshold(d, img.copy(), r, c)
-                        assert_same(d, oracle.adaptive_threshold(img, r, c), "gs_adaptive_threshold r=%d c=%d T=%d img %d" % (r, c, T, k))
-            emu.tune(0, 0)
-            emu.tune(6, 4)  # the any-radius kernel on the same input
-            d = np.zeros_like(imgs[0])
-            emu.blur(d, imgs[0].copy(), r)
-            assert_same(d, oracle.blur(imgs[0], r), "k_box16 gs_blur r=%d" % r)
-            d = np.zeros_like(imgs[0])
-            emu.adaptive_threshold(d, imgs[0].copy(), r, 5)
-            assert_same(d, oracle.adaptive_threshold(imgs[0], r, 5), "k_box16 gs_adaptive_threshold r=%d" % r)
-            emu.tune(6, 0)
-    finally:
-        emu.tune(0, 0)
-        emu.tune(6, 0)
+    for r in kl.ring_radii(shape):  # shorter frames take k_box16 (covered by the any-radius tests)
+        kl.box_ring(emu, oracle, (MEM,), shape, r)
 
 
 def test_box_kernel_any_band_height_and_full_width(emu, oracle):
     """k_box16 with bands of 1 .. 200 rows (gsh_tune key 0; the launcher itself picks 8 .. h) on a batch, and on rows as
     wide as the kernel goes (4096 = 256 threads x 16 px) with radii on both sides of every switch"""
-    rng = np.random.RandomState(11)
-    img = rng.randint(0, 256, (3, 50, 64)).astype(np.uint8)
-    try:
-        for T in (1, 2, 3, 8, 17, 50, 200):
-            emu.tune(0, T)
-            for r in (4, 9, 20):
-                d = np.zeros_like(img)
-                emu.blur_batch(d, img, r)
-                for f in range(3):
-                    assert_same(d[f], oracle.blur(img[f], r), "band height %d, r=%d, frame %d" % (T, r, f))
-    finally:
-        emu.tune(0, 0)
-    for (w, h) in ((4096, 4), (4080, 3)):
-        wide = rng.randint(0, 256, (h, w)).astype(np.uint8)
-        for r in (4, 31, 32, 127):
-            d = np.zeros_like(wide)
-            emu.blur(d, wide.copy(), r)
-            assert_same(d, oracle.blur(wide, r), "gs_blur r=%d %dx%d" % (r, w, h))
-            d = np.zeros_like(wide)
-            emu.adaptive_threshold(d, wide.copy(), r, 3)
-            assert_same(d, oracle.adaptive_threshold(wide, r, 3), "gs_adaptive_threshold r=%d %dx%d" % (r, w, h))
+    kl.box_band_heights(emu, oracle, MEM)
+    for shape in kl.FULL_WIDTH_SHAPES:
+        kl.box_full_width(emu, oracle, (MEM,), shape)

@@ -1,7 +1,12 @@
 """Parity tests proper: the HIP path on a real MI355X, called through the C ABI, against the CPU
 oracle on the same seeded inputs -- bit-exact for every integer/byte/index output; the ORB angle
 is within 1e-5 (and in fact identical bits, same host libm).  Also the reference-generated golden
-vectors at BASELINE.json's full sizes and size-independent properties on batches."""
+vectors at BASELINE.json's full sizes and size-independent properties on batches.
+
+This module repeats a thinner selection of tests/test_emu_logic.py at larger shapes.  The dense sweeps of that module -- every
+ring radius of k_box16r in both modes, the compare constants around every clamp, FAST's wrap thresholds, the histogram
+alignments, the launch-tuning keys of the strip kernels, gs_compute_orientation beyond r = 36 -- run on the MI355X in
+tests/test_gpu_kernel_logic.py, from the bodies both back ends share (tests/kernel_logic_cases.py)."""
 import os
 import subprocess
 
